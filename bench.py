@@ -2,6 +2,7 @@
 """Headline benchmark: SpMM GEdges/s + achieved-HBM fraction.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--op spmm_sum] [--config c3|c4] [--scaling strong|weak]
+                    [--dump-outputs DIR] [--full]
 
 N = 1 (default): BASELINE.json config 3 — random CSR, 2M x 2M, nnz = 20M,
 dense F = 128 fp32, one `spmm_sum` forward per step, inputs resident in HBM.
@@ -17,10 +18,20 @@ the block's per-matrix plan (paddle_sparse_amd.distributed.RowPartitionedSpMM):
       N*2M nodes) and the matching block of B; c4 runs F = 256: at 8 GPUs
       BASELINE config 4 (16M x 16M, 160M entries).
 
-Prints ONE JSON line on rank 0 (contract in the task brief): whole-job
-GEdges/s, the roofline object of the dominant kernel (algorithmic bytes /
-HIP-event kernel time vs 8 TB/s) and the CPU baseline (oracle C port timed on
-this box's host cores).
+Prints ONE JSON line on rank 0: whole-job GEdges/s over the K timed steps and
+ms_per_step.  A plain run does only that: set-up, W warm-up steps, K timed
+steps, the dump of --dump-outputs, the line.  --full adds, after the timed
+steps, everything else this file measures: the roofline object of the dominant
+kernel (algorithmic bytes / HIP-event kernel time of a run of its own vs
+8 TB/s), the CPU baseline (oracle C port timed on the host cores) with the
+check of the GPU result against it, the other config-3 ops, config 2 and the
+power-law graphs (N = 1), and at N > 1 the forms that were not timed.
+
+--dump-outputs DIR writes what the last timed step returned (out, and arg_out
+for min / max) as DIR/<name>.npy, float32 (arg_out as float64), `_rank<r>` in
+the name at N > 1.  Outputs above DUMP_BYTES keep a fixed sample of their rows
+(numpy seed 0); the inputs come from fixed seeds, so two builds run with the
+same flags can be compared file by file.
 """
 from __future__ import annotations
 
@@ -50,6 +61,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec peak
 M_PER_GPU = 2_000_000
 NNZ_PER_GPU = 20_000_000
 FEAT = 128
+DUMP_BYTES = 48 << 20  # --dump-outputs: all files of all ranks together stay below this
 
 
 def algorithmic_bytes(nnz: int, M: int, F: int, has_value: bool = True, arg_out: bool = False) -> int:
@@ -127,6 +139,30 @@ def event_ms(fn, reps: int) -> float:
     b.record()
     torch.cuda.synchronize()
     return a.elapsed_time(b) / reps
+
+
+def dump_outputs(result, outdir: Path, world: int, rank: int) -> list:
+    """--dump-outputs: the arrays one step returned (a tensor, or spmm_min / spmm_max's (out, arg_out)) as
+    outdir/<name>.npy — float32, an int64 arg_out as float64 (exact).  When the rows of every rank together would
+    pass DUMP_BYTES, the same sorted sample of rows (numpy seed 0, drawn from the row count alone) is kept of every
+    array.  Returns the paths written."""
+    arrays = result if isinstance(result, tuple) else (result,)
+    arrays = [(name, a) for name, a in zip(("out", "arg_out"), arrays) if a is not None]
+    rows = arrays[0][1].shape[0]
+    row_bytes = sum((8 if a.dtype == torch.int64 else 4) * (a.numel() // max(rows, 1)) for _, a in arrays)
+    keep = min(rows, DUMP_BYTES // (world * max(row_bytes, 1)))
+    sel = None
+    if keep < rows:
+        sel = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+        sel = torch.from_numpy(sel).to(arrays[0][1].device)
+    written = []
+    for name, a in arrays:
+        a = a if sel is None else a.index_select(0, sel)
+        a = a.to(torch.float64 if a.dtype == torch.int64 else torch.float32).cpu().numpy()
+        path = outdir / (f"{name}_rank{rank}.npy" if world > 1 else f"{name}.npy")
+        np.save(path, a)
+        written.append(path)
+    return written
 
 
 def rmat_graph(scale: int, n: int, device, seed: int = 4, relabel: bool = False):
@@ -475,8 +511,15 @@ def main(argv=None) -> None:
                     help="N > 1.  strong: the ONE config-3 matrix split by nnz over the N ranks (BASELINE.json's metric: "
                          "'2M-node nnz=20M F=128, 1/2/4/8 GPU'); weak: 2M rows / 20M entries PER GPU, columns over all "
                          "N x 2M nodes (config 4's structure).  auto = strong for c3, weak for c4")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the breadth / power-law legs after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: the dominant kernel alone "
+                         "(roofline), the CPU baseline and the check against it, the breadth / power-law legs and, at "
+                         "N > 1, the forms that were not timed")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned to DIR/<name>.npy (float32 / float64; a seeded sample "
+                         f"of rows past {DUMP_BYTES >> 20} MiB in all)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the breadth / power-law legs after the timed region")
     ap.add_argument("--exchange", default="auto", choices=["auto", "full", "full_p2p", "halo"],
                     help="N > 1: all of B by all-gather, the same by direct peer copies, or only the rows this rank's "
                          "columns touch (all_to_all_single); auto times full and halo before the warmup "
@@ -491,6 +534,8 @@ def main(argv=None) -> None:
     ap.add_argument("--no-plan", action="store_true", help="N > 1: rank-local kernel on the raw arrays (algo auto) "
                                                            "instead of the block's per-matrix plan")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "LOCAL_RANK" not in os.environ and os.environ.get("WORLD_SIZE", "1") != str(args.gpus):
         # typed without a launcher (torch.distributed.run gives every rank LOCAL_RANK; a stray WORLD_SIZE=1 in the
@@ -501,6 +546,10 @@ def main(argv=None) -> None:
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
+    dump_dir = None
+    if args.dump_outputs:  # made before any GPU work: a directory that cannot be written fails the run at once
+        dump_dir = Path(args.dump_outputs)
+        dump_dir.mkdir(parents=True, exist_ok=True)
 
     load_compute_modules()
     if not torch.cuda.is_available():
@@ -648,18 +697,22 @@ def main(argv=None) -> None:
         out = step()
     sync_all()
     elapsed = time.perf_counter() - t0
+    if dump_dir is not None:  # before anything else runs: a keep_output buffer (N > 1) is written again below
+        for path in dump_outputs(out, dump_dir, world, rank):
+            print(f"[bench] wrote {path}", file=sys.stderr, flush=True)
     if isinstance(out, tuple):
         out = out[0]
 
-    # dominant kernel alone (HIP events on its launch stream), after the timed region
-    kern_ms = event_ms(local_kernel, args.steps)
+    # dominant kernel alone (HIP events on its launch stream), after the timed region (--full only: the
+    # roofline is the one consumer; a plain run reports 0 here and leaves the roofline out of its line)
+    kern_ms = event_ms(local_kernel, args.steps) if args.full else 0.0
 
     # SURVEY.md §8(e) asks for the local-kernel aggregate, end-to-end serial and end-to-end
     # overlapped: the forms that were NOT timed above run a few steps here, so the line carries all.
     form_s = {}
     exch_ms = {}
     kern_by_exchange = {}
-    if use_dist:
+    if use_dist and args.full:
         other_steps = max(TUNE_STEPS, args.steps // 2)
         for key, o in forms.items():
             if key == chosen:
@@ -697,12 +750,13 @@ def main(argv=None) -> None:
         my_alg = algorithmic_bytes(nnz, M, F, True, minmax)
     roof_rank, roof_ms, roof_alg, roof_nnz = 0, kern_ms_own, my_alg, nnz
     if use_dist:
-        # the roofline pairs ONE rank's kernel time with that same rank's bytes: the slowest rank's
-        kr = torch.zeros(world, 3, dtype=torch.float64, device=device)
-        kr[rank, 0], kr[rank, 1], kr[rank, 2] = kern_ms_own, float(my_alg), float(nnz)
-        dist.all_reduce(kr)
-        roof_rank = int(kr[:, 0].argmax())
-        roof_ms, roof_alg, roof_nnz = float(kr[roof_rank, 0]), int(kr[roof_rank, 1]), int(kr[roof_rank, 2])
+        if args.full:
+            # the roofline pairs ONE rank's kernel time with that same rank's bytes: the slowest rank's
+            kr = torch.zeros(world, 3, dtype=torch.float64, device=device)
+            kr[rank, 0], kr[rank, 1], kr[rank, 2] = kern_ms_own, float(my_alg), float(nnz)
+            dist.all_reduce(kr)
+            roof_rank = int(kr[:, 0].argmax())
+            roof_ms, roof_alg, roof_nnz = float(kr[roof_rank, 0]), int(kr[roof_rank, 1]), int(kr[roof_rank, 2])
         rr = torch.tensor([o.rows_received_per_step() for o in ops_by_exchange.values()], dtype=torch.int64, device=device)
         dist.all_reduce(rr, op=dist.ReduceOp.MAX)
         recv_rows = dict(zip(ops_by_exchange, rr.tolist()))
@@ -714,15 +768,6 @@ def main(argv=None) -> None:
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = total_nnz / (elapsed / args.steps) / 1e9
-        alg = roof_alg
-        achieved = alg / (roof_ms * 1e-3) / 1e9
-        traffic, traffic_note = None, "not collected for this configuration"
-        tfile = ROOT / "profiles" / "traffic.json"
-        if tfile.exists() and world == 1 and args.config == "c3" and not half:
-            rec = json.loads(tfile.read_text()).get(f"{args.op}_c3", {})
-            traffic = rec.get("hbm_bytes_per_launch")
-            traffic_note = (f"read from profiles/traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of round "
-                            f"{rec.get('round', '?')}, {rec.get('source', '?')}); not measured in this run")
         if use_dist and scaling == "strong":
             what = (f"{args.op} fwd, the ONE uniform random CSR {M_PER_GPU}x{N} with nnz={total_nnz} "
                     f"({'a tenth of BASELINE config 3: rehearsal' if rehearse else 'BASELINE config 3'}), "
@@ -756,7 +801,19 @@ def main(argv=None) -> None:
                 "rows_per_gpu": M, "nnz_per_gpu": nnz, "feat": F, "index_dtype": "int64",
                 "variant": args.variant,
             },
-            "roofline": {
+            "full": args.full,  # False: the line holds the headline only (see the module docstring)
+        }
+        if args.full:
+            alg = roof_alg
+            achieved = alg / (roof_ms * 1e-3) / 1e9
+            traffic, traffic_note = None, "not collected for this configuration"
+            tfile = ROOT / "profiles" / "traffic.json"
+            if tfile.exists() and world == 1 and args.config == "c3" and not half:
+                rec = json.loads(tfile.read_text()).get(f"{args.op}_c3", {})
+                traffic = rec.get("hbm_bytes_per_launch")
+                traffic_note = (f"read from profiles/traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of round "
+                                f"{rec.get('round', '?')}, {rec.get('source', '?')}); not measured in this run")
+            line["roofline"] = {
                 "bound": "hbm",
                 "kernel": "spmm_half_row_kernel" if half else "spmm_fused_kernel",
                 "achieved": round(achieved, 1),
@@ -768,53 +825,59 @@ def main(argv=None) -> None:
                 "algorithmic_bytes_per_launch": alg,
                 "kernel_ms": round(roof_ms, 4),
                 "kernel_gedges_per_s": round(roof_nnz / (roof_ms * 1e-3) / 1e9, 4),
-            },
-        }
+            }
         if rehearse:
             line["rehearsal"] = (f"{world} ranks sharing ONE GPU over gloo (PSA_BENCH_REHEARSE_ON_ONE_GPU=1): a functional run of "
                                  "the N > 1 path; none of its times is a measurement")
         if use_dist:
-            rate = lambda s_: round(total_nnz / s_ / 1e9, 4)  # noqa: E731
-            serial = {e: rate(form_s[(e, 1)]) for e in ops_by_exchange if (e, 1) in form_s}
-            overl = {e: rate(form_s[(e, c)]) for (e, c) in form_s if c > 1}
             line["config"]["rows_nnz_by_rank"] = shard_sizes
-            line["roofline"]["note"] = (f"rank {roof_rank}'s block (the slowest rank's kernel): its own algorithmic bytes "
-                                        "over its own HIP-event kernel time")
-            line["multi_gpu"] = {
+            mg = {
                 "form_timed_as_value": f"{chosen[0]}/chunks{chosen[1]}",
                 "form_chosen_by": "flags" if len(forms) == 1 else f"{TUNE_STEPS} steady-state steps per form before the warmup (ms per step by form)",
                 "tune_ms_per_step_by_form": tune_ms or None,
-                "step_ms_by_form": {f"{e}/chunks{c}": round(x * 1e3, 4) for (e, c), x in form_s.items()},
-                "local_plan": "raw arrays, algo auto" if args.no_plan else op.local_storage()._spmm_algo(),
-                "spmm_only_aggregate_gedges_per_s": rate(kern_ms * 1e-3),
-                "end_to_end_serial_gedges_per_s": serial,
-                "end_to_end_overlapped_gedges_per_s": overl,
-                "overlapped_feature_chunks": 4,
-                "exchange_ms": {e: round(x, 4) for (e, c), x in exch_ms.items() if c == 1},
-                "exchange_ms_by_form": {f"{e}/chunks{c}": round(x, 4) for (e, c), x in exch_ms.items()},
-                "kernel_ms_by_form": {f"{e}/chunks{c}": round(x, 4) for (e, c), x in kern_by_exchange.items()},
-                "kernel_plus_exchange_ms_by_form": {f"{e}/chunks{c}": round(exch_ms[(e, c)] + kern_by_exchange[(e, c)], 4)
-                                                    for (e, c) in exch_ms},
-                "step_over_parts_by_form": {f"{e}/chunks{c}": round(form_s[(e, c)] * 1e3 / (exch_ms[(e, c)] + kern_by_exchange[(e, c)]), 4)
-                                            for (e, c) in exch_ms},
+            }
+            if args.full:
+                rate = lambda s_: round(total_nnz / s_ / 1e9, 4)  # noqa: E731
+                serial = {e: rate(form_s[(e, 1)]) for e in ops_by_exchange if (e, 1) in form_s}
+                overl = {e: rate(form_s[(e, c)]) for (e, c) in form_s if c > 1}
+                line["roofline"]["note"] = (f"rank {roof_rank}'s block (the slowest rank's kernel): its own algorithmic bytes "
+                                            "over its own HIP-event kernel time")
+                mg["step_ms_by_form"] = {f"{e}/chunks{c}": round(x * 1e3, 4) for (e, c), x in form_s.items()}
+            mg["local_plan"] = "raw arrays, algo auto" if args.no_plan else op.local_storage()._spmm_algo()
+            if args.full:
+                mg.update({
+                    "spmm_only_aggregate_gedges_per_s": rate(kern_ms * 1e-3),
+                    "end_to_end_serial_gedges_per_s": serial,
+                    "end_to_end_overlapped_gedges_per_s": overl,
+                    "overlapped_feature_chunks": 4,
+                    "exchange_ms": {e: round(x, 4) for (e, c), x in exch_ms.items() if c == 1},
+                    "exchange_ms_by_form": {f"{e}/chunks{c}": round(x, 4) for (e, c), x in exch_ms.items()},
+                    "kernel_ms_by_form": {f"{e}/chunks{c}": round(x, 4) for (e, c), x in kern_by_exchange.items()},
+                    "kernel_plus_exchange_ms_by_form": {f"{e}/chunks{c}": round(exch_ms[(e, c)] + kern_by_exchange[(e, c)], 4)
+                                                        for (e, c) in exch_ms},
+                    "step_over_parts_by_form": {f"{e}/chunks{c}": round(form_s[(e, c)] * 1e3 / (exch_ms[(e, c)] + kern_by_exchange[(e, c)]), 4)
+                                                for (e, c) in exch_ms},
+                })
+            mg.update({
                 "allgather_bytes_received_per_rank": recv_rows.get("full", 0) * F * esz,
                 "bytes_received_per_rank_by_exchange": {e: r * F * esz for e, r in recv_rows.items()},
                 "buffer_bytes_held_by_form_objects": {e: o.buffer_bytes() for e, o in ops_by_exchange.items()},
                 "note": "value counts the exchange of B inside every step, in the form named by form_timed_as_value; "
                         "spmm_only_* is the local-kernel rate with B already assembled (slowest rank)",
-            }
-        if (not args.no_cpu and args.op == "spmm_sum" and world == 1 and isinstance(B_full, torch.Tensor) and not half
-                and not (use_dist and chosen[0] == "halo")):  # CPU leg: N = 1 only
+            })
+            line["multi_gpu"] = mg
+        if (args.full and not args.no_cpu and args.op == "spmm_sum" and world == 1 and isinstance(B_full, torch.Tensor)
+                and not half and not (use_dist and chosen[0] == "halo")):  # CPU leg: N = 1 only
             info, ref, rows = cpu_baseline(rowptr, col, val, B_full)
             got = out[:rows].cpu().numpy()
             scale = np.abs(ref).max()
             line["cpu_baseline"] = info
             line["check_max_abs_err_vs_oracle"] = float(np.abs(got - ref).max() / scale)
-        if "cpu_baseline" not in line:
+        if args.full and "cpu_baseline" not in line:
             line["cpu_baseline"] = None
             line["cpu_baseline_note"] = ("the CPU leg runs on rank 0 at N = 1 with --op spmm_sum --dtype f32 only (here: "
                                          f"n_gpus={world}, op={args.op}, dtype={args.dtype}, no_cpu={args.no_cpu})")
-        if not args.no_extra and world == 1 and not use_dist and args.config == "c3" and not half:
+        if args.full and not args.no_extra and world == 1 and not use_dist and args.config == "c3" and not half:
             # after the timed region: the rest of BASELINE config 3 (mean / max forward, sum / max
             # forward + backward) and the forward on a power-law graph; headline fields unchanged
             line["c3_other_ops"] = breadth(rowptr, col, val, B_full, max(5, args.steps // 5))

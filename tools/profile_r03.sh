@@ -15,7 +15,7 @@ case $WHAT in
       bash tools/prof_pmc.sh $tag "$c" $REPO/tools/pmc_backward.py 3 | tee gpurun_out/$tag.txt
     done ;;
   breadth)
-    bash tools/prof_stats.sh r03_breadth $REPO/bench.py --steps 20 --warmup 5 --no-cpu | tee gpurun_out/r03_breadth_stats.txt
+    bash tools/prof_stats.sh r03_breadth $REPO/bench.py --full --steps 20 --warmup 5 --no-cpu
     cp gpurun_out/stats_r03_breadth/*/*_kernel_stats.csv gpurun_out/r03_kernel_stats_breadth.csv ;;
   traffic)
     # HBM bytes of the headline kernel: separate FETCH_SIZE / WRITE_SIZE / TCC passes over the bench command
