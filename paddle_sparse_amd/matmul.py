@@ -72,14 +72,16 @@ def _huge_piece_winners(st: SparseStorage, reduce: str, value: Optional[torch.Te
     reaches the row's extreme keeps its winner, every other piece says "no winner" (0xffff) — ties go to the
     earlier edge, as everywhere.  Returns int16[P, K]: what the pass over the CSC view reads for the entries of
     those rows (`_huge_backward_plan` points them at their pieces).  The extra work is one more gather of the
-    entries of the rows concerned; everything else is a few launches on [P, K] arrays.  (A row whose extreme is
-    NaN gets no winner here; the int64 route would name one.)"""
+    entries of the rows concerned; everything else is a few launches on [P, K] arrays."""
     hr = st._huge_rows()
     v = None if value is None else ops.gather_rows(value.detach(), hr["ids"])
     out_h, _, bytes_h = ops._spmm(reduce, hr["rowptr"], hr["col"], v, mat.detach(), want_arg=False, want_arg_bytes=2)
     piece_row, first_piece = hr["piece_row"], hr["piece_ptr"][:-1]
-    best = ops.segment_csr(out_h, hr["piece_ptr"], reduce)  # [H, K]: the rows' extremes (== out[rows])
-    eq = out_h == best[piece_row]
+    # a piece in which no product beats the init names no winner (0xffff); whatever it left in out_h is no candidate
+    won = bytes_h != -1
+    lost = torch.full_like(out_h, float("inf") if reduce == "min" else float("-inf"))
+    best = ops.segment_csr(torch.where(won, out_h, lost), hr["piece_ptr"], reduce)  # [H, K]: the rows' extremes
+    eq = won & (out_h == best[piece_row])
     run = torch.cumsum(eq.to(torch.int32), 0)
     before = run[first_piece] - eq[first_piece].to(torch.int32)
     first = eq & ((run - before[piece_row]) == 1)

@@ -78,6 +78,13 @@ def _ptr(x: Optional[torch.Tensor]) -> Optional[int]:
     return None if x is None else x.data_ptr()
 
 
+def _aligned16(x: torch.Tensor) -> torch.Tensor:
+    """x itself when its data starts on a 16-byte boundary, else a contiguous copy (a fresh allocation is):
+    the vector kernels load 16 bytes at a time and their C-ABI refuses other operands.  A contiguous view
+    can start anywhere (flat[1:1 + N * K].view(N, K))."""
+    return x if x.data_ptr() % 16 == 0 else x.clone(memory_format=torch.contiguous_format)
+
+
 def sparse_cuda_version() -> torch.Tensor:
     """csrc/version.cpp:14-22: int64[1] on the CPU; -1 on this (HIP) build."""
     return torch.full((1,), _lib.load().psa_sparse_cuda_version(), dtype=torch.int64)
@@ -158,6 +165,7 @@ def _spmm(reduce: str, rowptr: torch.Tensor, col: torch.Tensor,
         if hot_rows.dtype != torch.float32 or hot_rows.dim() != 2 or hot_rows.shape[1] != K or not hot_rows.is_contiguous():
             raise ValueError("hot_rows must be a contiguous float32 [h, K] tensor")
         num_hot = hot_rows.shape[0]
+        mat = _aligned16(mat)  # the redirected column ids are served by the edge-range kernels only (16-byte rows)
     ldo = 0
     if out is None:
         out = torch.empty((M, K), dtype=torch.float32, device=mat.device)
@@ -185,7 +193,9 @@ def _spmm(reduce: str, rowptr: torch.Tensor, col: torch.Tensor,
     # fall back to the row path on shapes they do not take).  Behind the others the
     # bytes are derived from arg_out, which must then exist.  (ws_bytes > 0 is not the
     # test: it also covers the edge-range scratch, which every nnz > 0 has.)
-    bytes_in_kernel = K % 4 == 0 and (K <= 64 or (K <= 256 and nnz > LONG_ROW))
+    # (those kernels read 16-byte rows: a misaligned `mat` or `out` sends the shape to the 1-wide kernels, which do not)
+    vec4 = K % 4 == 0 and mat.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0 and (ldo == 0 or ldo % 4 == 0)
+    bytes_in_kernel = vec4 and (K <= 64 or (K <= 256 and nnz > LONG_ROW))
     if minmax and want_arg_bytes and K % 4 == 0 and K <= 256 and not bytes_in_kernel:
         want_arg = True
     if minmax and want_arg:
@@ -225,6 +235,7 @@ def _spmm_half(reduce: str, rowptr, col, value, mat, want_arg: bool = True, row=
     if K % 8 != 0:
         res = _spmm(reduce, rowptr, col, None if value is None else value.float(), mat.float(), want_arg=want_arg)
         return res[0].to(mat.dtype), res[1]
+    mat = _aligned16(mat)  # 16-byte gathers of 8 elements
     out = torch.empty((M, K), dtype=mat.dtype, device=mat.device)
     arg = torch.empty((M, K), dtype=torch.int64, device=mat.device) if minmax and want_arg else None
     if algo == "edge_ranges" and nnz > 0 and (value is None or value.dtype == torch.float32):
@@ -990,7 +1001,7 @@ def spmm_minmax_bw_csc(rowptr, colptr, row_csc, csr2csc, tag, value, mat, grad, 
     65 535 entries, SparseStorage._huge_backward_plan)."""
     rowptr, colptr = _index(rowptr, "rowptr"), _index(colptr, "colptr")
     row_csc, csr2csc = _index(row_csc, "row_csc"), _index(csr2csc, "csr2csc")
-    grad = _f32(grad, "grad")
+    grad = _aligned16(_f32(grad, "grad"))
     if arg_out is None and arg_bytes is None:
         raise ValueError("spmm_minmax_bw_csc needs arg_out or arg_bytes")
     if arg_out is not None:
@@ -1024,7 +1035,7 @@ def spmm_minmax_bw_csc(rowptr, colptr, row_csc, csr2csc, tag, value, mat, grad, 
         hot_grad, hot_bytes = _gather_rows_raw(grad, hot_ids), _hot_bytes(arg_bytes, hot_ids, hot_bytes_tail)
     gv = None
     if want_value:
-        mat = _f32(mat, "mat")
+        mat = _aligned16(_f32(mat, "mat"))
         if mat.shape != (N, K):
             raise ValueError("mat must be [N, K]")
         gv = torch.empty(nnz, dtype=torch.float32, device=grad.device)
@@ -1070,7 +1081,7 @@ def spmm_minmax_bw_eb(colptr, col_csc, row_csc, tag, weight_csc, grad, arg_bytes
     colptr, row_csc = _index(colptr, "colptr"), _index(row_csc, "row_csc")
     if col_csc is not None:
         col_csc = _index(col_csc, "col_csc")
-    grad = _f32(grad, "grad")
+    grad = _aligned16(_f32(grad, "grad"))
     _gpu(tag, "tag")
     _gpu(arg_bytes, "arg_bytes")
     if tag.dtype not in (torch.uint8, torch.int16) or arg_bytes.dtype != tag.dtype or arg_bytes.shape != grad.shape:
@@ -1105,7 +1116,7 @@ def spmm_sum_bw_csc(colptr, row_csc, csr2csc, value, mat, grad, want_value: bool
     (f32[M]): it multiplies both gradients per edge.  hot_ids: int64[h] rows of grad
     that row_csc refers to as M + position (a compact copy is gathered here)."""
     colptr, row_csc, csr2csc = _index(colptr, "colptr"), _index(row_csc, "row_csc"), _index(csr2csc, "csr2csc")
-    grad = _f32(grad, "grad")
+    grad = _aligned16(_f32(grad, "grad"))
     if value is not None:
         value = _f32(value, "value")
     (M, K), N, nnz = grad.shape, colptr.numel() - 1, csr2csc.numel()
@@ -1126,7 +1137,7 @@ def spmm_sum_bw_csc(colptr, row_csc, csr2csc, value, mat, grad, want_value: bool
             row_scale = torch.cat([row_scale, row_scale[hot_ids]])
     gv = None
     if want_value:
-        mat = _f32(mat, "mat")
+        mat = _aligned16(_f32(mat, "mat"))
         if mat.shape != (N, K):
             raise ValueError("mat must be [N, K]")
         gv = torch.empty(nnz, dtype=torch.float32, device=grad.device)
@@ -1169,7 +1180,7 @@ def spmm_half_sum_bw_csc(colptr, row_csc, weight_csc, mat, grad, want_value: boo
     _gpu(grad, "grad")
     if grad.dtype not in (torch.float16, torch.bfloat16) or grad.dim() != 2:
         raise TypeError("grad must be a 2-D float16 / bfloat16 tensor")
-    grad = grad.contiguous()
+    grad = _aligned16(grad.contiguous())
     (M, K), N, nnz = grad.shape, colptr.numel() - 1, row_csc.numel()
     if weight_csc is not None:
         weight_csc = _f32(weight_csc, "weight_csc")
@@ -1182,7 +1193,7 @@ def spmm_half_sum_bw_csc(colptr, row_csc, weight_csc, mat, grad, want_value: boo
         _gpu(mat, "mat")
         if mat.dtype != grad.dtype or mat.shape != (N, K):
             raise ValueError("mat must be [N, K] in grad's dtype")
-        mat = mat.contiguous()
+        mat = _aligned16(mat.contiguous())
         gv = torch.empty(nnz, dtype=torch.float32, device=grad.device)
     gm = torch.empty((N, K), dtype=grad.dtype, device=grad.device)
     ws = _half_long_workspace(K, nnz, grad.device, long_columns)
@@ -1203,7 +1214,7 @@ def spmm_half_minmax_bw_csc(colptr, row_csc, tag, weight_csc, mat, grad, arg_byt
     _gpu(grad, "grad")
     if grad.dtype not in (torch.float16, torch.bfloat16) or grad.dim() != 2:
         raise TypeError("grad must be a 2-D float16 / bfloat16 tensor")
-    grad = grad.contiguous()
+    grad = _aligned16(grad.contiguous())
     (M, K), N, nnz = grad.shape, colptr.numel() - 1, row_csc.numel()
     _gpu(tag, "tag")
     _gpu(arg_bytes, "arg_bytes")
@@ -1217,7 +1228,7 @@ def spmm_half_minmax_bw_csc(colptr, row_csc, tag, weight_csc, mat, grad, arg_byt
         _gpu(mat, "mat")
         if mat.dtype != grad.dtype or mat.shape != (N, K):
             raise ValueError("mat must be [N, K] in grad's dtype")
-        mat = mat.contiguous()
+        mat = _aligned16(mat.contiguous())
         gv = torch.empty(nnz, dtype=torch.float32, device=grad.device)
     gm = torch.empty((N, K), dtype=grad.dtype, device=grad.device)
     ws = _half_long_workspace(K, nnz, grad.device, long_columns)

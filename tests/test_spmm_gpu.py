@@ -171,25 +171,53 @@ def test_ties_pick_first_edge():
         assert np.all(out == 5.0) and np.all(arg == 0)
 
 
+def integer_data(val, B, seed):
+    """The `int` mode of tests/exact_ref.py on the same shapes: value in [-3, 3], B in [-8, 8] — every fp32 sum
+    exact, so the kernels must give the exact reference's bits (and min / max see many ties)."""
+    rng = np.random.default_rng(seed)
+    val = None if val is None else rng.integers(-3, 4, val.shape).astype(np.float32)
+    return val, rng.integers(-8, 9, B.shape).astype(np.float32)
+
+
+def check_exact(reduce, rowptr, col, val, B):
+    from exact_ref import assert_exact_preconditions, spmm_ref
+
+    t = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a))
+    assert_exact_preconditions(t(rowptr), t(col), t(val), t(B))
+    out, arg = run_gpu(reduce, rowptr, col, val, B)
+    ref, ref_arg = spmm_ref(reduce, t(rowptr), t(col), t(val), t(B))
+    assert np.array_equal(out, ref.numpy())
+    if ref_arg is not None:
+        assert np.array_equal(arg, ref_arg.numpy())
+
+
+# data: standard normal (tolerance against the oracle), then the `int` mode of tests/exact_ref.py on the same shapes
+# (bit-equal to the exact reference) — a loop in the body rather than a parameter, so the test ids stay as they were
 @pytest.mark.parametrize("variant", [0, 2, 3, 4, 16, 17, 18])  # 17: ordinary stores, 18: non-temporal gathers
 def test_variants_k128(variant):
     from paddle_sparse_amd import ops
 
     once()
 
-    row, rowptr, col, val = random_csr(3000, 2000, 40000, seed=variant)
-    B = np.random.default_rng(5).standard_normal((2000, 128)).astype(np.float32)
-    prev = ops.spmm_set_variant(variant)
-    try:
-        for reduce in ("sum", "mean", "max"):
-            check(reduce, rowptr, col, val, B)
-        if variant >= 16:  # memory-path variants of the production kernel: same arithmetic, same bits
-            got = run_gpu("max", rowptr, col, val, B)
-            ops.spmm_set_variant(0)
-            ref = run_gpu("max", rowptr, col, val, B)
-            assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1])
-    finally:
-        ops.spmm_set_variant(prev)
+    for data in ("normal", "int"):
+        row, rowptr, col, val = random_csr(3000, 2000, 40000, seed=variant)
+        B = np.random.default_rng(5).standard_normal((2000, 128)).astype(np.float32)
+        if data == "int":
+            val, B = integer_data(val, B, variant)
+        prev = ops.spmm_set_variant(variant)
+        try:
+            for reduce in ("sum", "mean", "max"):
+                check(reduce, rowptr, col, val, B)
+            if data == "int":
+                for reduce in ("sum", "mean", "min", "max"):
+                    check_exact(reduce, rowptr, col, val, B)
+            if variant >= 16:  # memory-path variants of the production kernel: same arithmetic, same bits
+                got = run_gpu("max", rowptr, col, val, B)
+                ops.spmm_set_variant(0)
+                ref = run_gpu("max", rowptr, col, val, B)
+                assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1])
+        finally:
+            ops.spmm_set_variant(prev)
 
 
 @pytest.mark.parametrize("variant", [0, 1, 7, 11, 12, 13])
@@ -199,15 +227,22 @@ def test_multirow_variants_narrow_k(variant, K):
 
     once()
 
-    row, rowptr, col, val = skewed_csr(1000, 700, seed=K, long_rows=(0, 500, 999), long_deg=300)
-    B = np.random.default_rng(K).standard_normal((700, K)).astype(np.float32)
-    prev = ops.spmm_set_variant(variant)
-    try:
-        for reduce in ("sum", "mean", "min", "max"):
-            check(reduce, rowptr, col, val, B)
-        check("sum", rowptr, col, None, B)
-    finally:
-        ops.spmm_set_variant(prev)
+    for data in ("normal", "int"):
+        row, rowptr, col, val = skewed_csr(1000, 700, seed=K, long_rows=(0, 500, 999), long_deg=300)
+        B = np.random.default_rng(K).standard_normal((700, K)).astype(np.float32)
+        if data == "int":
+            val, B = integer_data(val, B, K)
+        prev = ops.spmm_set_variant(variant)
+        try:
+            for reduce in ("sum", "mean", "min", "max"):
+                check(reduce, rowptr, col, val, B)
+            check("sum", rowptr, col, None, B)
+            if data == "int":
+                for reduce in ("sum", "mean", "min", "max"):
+                    check_exact(reduce, rowptr, col, val, B)
+                check_exact("max", rowptr, col, None, B)
+        finally:
+            ops.spmm_set_variant(prev)
 
 
 @pytest.mark.parametrize("reduce", ["sum", "mean", "min", "max"])
