@@ -792,6 +792,48 @@ int psa_relabel_finish(const int64_t* idx, int64_t S, const int64_t* col,
                        const int64_t* rank, const int64_t* owner, int64_t n_out,
                        int64_t* n_id, int64_t* keys, psa_stream_t stream);
 
+/* ---- diagonal ops (torch_sparse/diag.py: remove_diag / set_diag / fill_diag / get_diag)
+ * on a SORTED CSR matrix (rowptr int64[M+1], col int64[nnz]).  The k-th diagonal is
+ * the cells (r, r + k) inside M x N; k outside (-M, N) has none.  Two calls and ONE
+ * host read, as the coalesce chain:
+ *   psa_diag_count(...)   new row lengths -> rowcount_out, rowptr_out (psa_count2ptr);
+ *                         nnz_out = rowptr_out[M] is the one value the caller reads back
+ *   psa_diag_write(...)   col_out int64[nnz_out], value_out [nnz_out, row_bytes]
+ * insert = 0: remove_diag (every stored (r, r + k) entry goes, duplicates included);
+ * insert = 1: set_diag (the same, then one entry per diagonal cell at its sorted place,
+ * value row diag_values[r - max(-k, 0)]).  Kept entries keep their order and bytes.
+ * colcount (int64[N] or NULL): the input's column counts; colcount_out then gets them
+ * adjusted for the removed / inserted entries.  workspace: psa_diag_workspace_bytes(M)
+ * bytes, 16-byte aligned; psa_diag_write reads what psa_diag_count left there.
+ * Deterministic, no atomics; the write pass is balanced by output entries. */
+size_t psa_diag_workspace_bytes(int64_t M);
+int psa_diag_count(const int64_t* rowptr, const int64_t* col, int64_t M, int64_t N, int64_t k, int insert,
+                   const int64_t* colcount, int64_t* rowcount_out, int64_t* rowptr_out, int64_t* colcount_out,
+                   void* workspace, size_t workspace_bytes, psa_stream_t stream);
+/* value: [nnz, row_bytes] of any dtype; value_out NULL (or row_bytes 0) for a value-less
+ * matrix.  value may be NULL when nnz is 0, diag_values when num_diag is 0.
+ * Gradient maps, each optional (NULL): out_pos int64[nnz] = output slot of every input
+ * entry, -1 for a removed one; diag_pos int64[num_diag] = output slot of every inserted
+ * entry.  The backward of the value path is psa_diag_gather through them. */
+int psa_diag_write(const int64_t* rowptr, const int64_t* col, const void* value, int64_t row_bytes,
+                   const void* diag_values, int64_t M, int64_t N, int64_t k, int insert, int64_t nnz,
+                   const int64_t* rowptr_out, int64_t nnz_out, const void* workspace, int64_t* col_out,
+                   void* value_out, int64_t* out_pos, int64_t* diag_pos, psa_stream_t stream);
+
+/* get_diag: out [min(M, N), row_bytes] = the value row of the LAST stored (r, r) entry of
+ * row r (storage order), zero bytes where there is none.  value NULL: out is
+ * f32[min(M, N)] of 1.0 / 0.0 (so a valued matrix passes a non-NULL value: nnz > 0).  pos_out (int64[min(M, N)] or NULL): that entry's
+ * position, -1 for none (the backward: psa_diag_scatter into zeros). */
+int psa_get_diag(const int64_t* rowptr, const int64_t* col, const void* value, int64_t row_bytes, int64_t M,
+                 int64_t N, void* out, int64_t* pos_out, psa_stream_t stream);
+
+/* out[i, :] = map[i] >= 0 ? src[map[i], :] : 0, rows of row_bytes bytes. */
+int psa_diag_gather(const void* src, const int64_t* map, int64_t n, int64_t row_bytes, void* out,
+                    psa_stream_t stream);
+/* out[pos[i], :] = src[i, :] for every pos[i] >= 0 (distinct); other rows of out untouched. */
+int psa_diag_scatter(const void* src, const int64_t* pos, int64_t n, int64_t row_bytes, void* out,
+                     psa_stream_t stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -10,6 +10,7 @@
 // There is no logic here beyond argument marshalling.
 #include <paddle/extension.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "paddle_sparse_hip.h"
@@ -892,3 +893,103 @@ PD_BUILD_OP(coalesce)
     .Outputs({"out_index", "out_value"})
     .Attrs({"m: int64_t", "n: int64_t", "reduce: int64_t"})
     .SetKernelFn(PD_KERNEL(coalesce));
+
+// ---- remove_diag / set_diag / get_diag (seam: torch_sparse/diag.py, paddle_sparse_amd/diag.py) ----
+// psa_diag_count -> one host read (rowptr'[M]) -> psa_diag_write, as the coalesce op.  The
+// input is a sorted CSR matrix with n columns; outputs rowptr', col', value' (empty when the
+// input has none), rowcount' and, when colcount is given, colcount' (else empty).
+// set_diag's `values` is [num_diag, ...] in value's dtype (the seam broadcasts and casts it;
+// absent = ones); fill_diag is set_diag with a filled `values`.
+static std::vector<paddle::Tensor> diag_rewrite(paddle::Tensor& rowptr, paddle::Tensor& col,
+                                                const paddle::optional<paddle::Tensor>& value,
+                                                const paddle::optional<paddle::Tensor>& colcount,
+                                                const paddle::optional<paddle::Tensor>& values, int64_t n, int64_t k,
+                                                bool insert) {
+  CHECK_GPU(rowptr);
+  CHECK_I64(rowptr);
+  CHECK_I64(col);
+  const int64_t m = rowptr.shape()[0] - 1;
+  const int64_t nnz = col.shape()[0];
+  void* s = stream_of(rowptr);
+  const auto place = rowptr.place();
+  auto rowcount = i64_empty(m, place);
+  auto rowptr_out = i64_empty(m + 1, place);
+  auto colcount_out = i64_empty(colcount ? n : 0, place);
+  const size_t ws_bytes = psa_diag_workspace_bytes(m);
+  auto ws = scratch(ws_bytes, place);
+  PSA_CALL(psa_diag_count(i64(rowptr), i64(col), m, n, k, insert ? 1 : 0, i64_or_null(colcount),
+                          rowcount.data<int64_t>(), rowptr_out.data<int64_t>(),
+                          colcount ? colcount_out.data<int64_t>() : nullptr, ws.data<uint8_t>(), ws_bytes, s));
+  const int64_t nnz_out = read_i64(rowptr_out, m, 1)[0];  // the one host read
+  auto col_out = i64_empty(nnz_out, place);
+  auto shape = value ? value.get().shape() : std::vector<int64_t>{0};
+  shape[0] = value ? nnz_out : 0;
+  auto value_out = paddle::empty(shape, value ? value.get().dtype() : paddle::DataType::FLOAT32, place);
+  const int64_t row_bytes =
+      value ? row_elems(value.get()) * static_cast<int64_t>(paddle::SizeOf(value.get().dtype())) : 0;
+  const void* diag_values = nullptr;
+  paddle::Tensor ones;
+  if (value && insert) {
+    const int64_t num_diag = std::max<int64_t>(k >= 0 ? std::min(m, n - k) : std::min(m + k, n), 0);
+    if (values) {
+      PD_CHECK(values.get().dtype() == value.get().dtype() && values.get().shape()[0] == num_diag,
+               "set_diag: values must be [num_diag, ...] in the value dtype");
+      diag_values = values.get().data();
+    } else {
+      auto ones_shape = value.get().shape();
+      ones_shape[0] = num_diag;
+      ones = paddle::full(ones_shape, 1, value.get().dtype(), place);
+      diag_values = ones.data();
+    }
+  }
+  PSA_CALL(psa_diag_write(i64(rowptr), i64(col), value ? value.get().data() : nullptr, row_bytes, diag_values, m, n,
+                          k, insert ? 1 : 0, nnz, rowptr_out.data<int64_t>(), nnz_out, ws.data<uint8_t>(),
+                          col_out.data<int64_t>(), value ? value_out.data() : nullptr, nullptr, nullptr, s));
+  return {rowptr_out, col_out, value_out, rowcount, colcount_out};
+}
+
+std::vector<paddle::Tensor> remove_diag(paddle::Tensor& rowptr, paddle::Tensor& col,
+                                        const paddle::optional<paddle::Tensor>& value,
+                                        const paddle::optional<paddle::Tensor>& colcount, int64_t n, int64_t k) {
+  return diag_rewrite(rowptr, col, value, colcount, paddle::optional<paddle::Tensor>(), n, k, false);
+}
+PD_BUILD_OP(remove_diag)
+    .Inputs({"rowptr", "col", paddle::Optional("value"), paddle::Optional("colcount")})
+    .Outputs({"rowptr_out", "col_out", "value_out", "rowcount_out", "colcount_out"})
+    .Attrs({"n: int64_t", "k: int64_t"})
+    .SetKernelFn(PD_KERNEL(remove_diag));
+
+std::vector<paddle::Tensor> set_diag(paddle::Tensor& rowptr, paddle::Tensor& col,
+                                     const paddle::optional<paddle::Tensor>& value,
+                                     const paddle::optional<paddle::Tensor>& colcount,
+                                     const paddle::optional<paddle::Tensor>& values, int64_t n, int64_t k) {
+  return diag_rewrite(rowptr, col, value, colcount, values, n, k, true);
+}
+PD_BUILD_OP(set_diag)
+    .Inputs({"rowptr", "col", paddle::Optional("value"), paddle::Optional("colcount"), paddle::Optional("values")})
+    .Outputs({"rowptr_out", "col_out", "value_out", "rowcount_out", "colcount_out"})
+    .Attrs({"n: int64_t", "k: int64_t"})
+    .SetKernelFn(PD_KERNEL(set_diag));
+
+// get_diag: [min(m, n), ...] main diagonal (last stored entry of a duplicated cell, zero where
+// none); float32 ones for a value-less matrix.
+std::vector<paddle::Tensor> get_diag(paddle::Tensor& rowptr, paddle::Tensor& col,
+                                     const paddle::optional<paddle::Tensor>& value, int64_t n) {
+  CHECK_GPU(rowptr);
+  CHECK_I64(rowptr);
+  CHECK_I64(col);
+  const int64_t m = rowptr.shape()[0] - 1;
+  auto shape = value ? value.get().shape() : std::vector<int64_t>{0};
+  shape[0] = std::min(m, n);
+  auto out = paddle::empty(shape, value ? value.get().dtype() : paddle::DataType::FLOAT32, rowptr.place());
+  const int64_t row_bytes =
+      value ? row_elems(value.get()) * static_cast<int64_t>(paddle::SizeOf(value.get().dtype())) : 0;
+  PSA_CALL(psa_get_diag(i64(rowptr), i64(col), value ? value.get().data() : nullptr, row_bytes, m, n, out.data(),
+                        nullptr, stream_of(rowptr)));
+  return {out};
+}
+PD_BUILD_OP(get_diag)
+    .Inputs({"rowptr", "col", paddle::Optional("value")})
+    .Outputs({"out"})
+    .Attrs({"n: int64_t"})
+    .SetKernelFn(PD_KERNEL(get_diag));

@@ -60,6 +60,7 @@ if not _running_the_builder():
         ("transpose", ("transpose", "t")),
         ("matmul", ("spmm", "matmul")),
         ("spspmm", ("spspmm",)),
+        ("diag", ("remove_diag", "set_diag", "fill_diag", "get_diag")),
     )
 
     __all__ = ["__version__"]

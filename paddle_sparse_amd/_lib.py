@@ -137,6 +137,15 @@ SIGNATURES = {
     "psa_spspmm_expand": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
                                   c_void_p, c_void_p]),
+    "psa_diag_workspace_bytes": (c_size_t, [c_int64]),
+    "psa_diag_count": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_size_t, c_void_p]),
+    "psa_diag_write": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int,
+                               c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
+    "psa_get_diag": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "psa_diag_gather": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "psa_diag_scatter": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1363,3 +1363,134 @@ def sample_adj(rowptr: torch.Tensor, col: torch.Tensor, idx: torch.Tensor, num_n
     keys, perm = index_sort(keys, max(S * n_out, 1), with_sorted_inputs=True, check=True)
     _, out_col = split_keys(keys, n_out, want_hi=False)
     return out_rowptr, out_col, n_id, gather_rows(e_raw, perm)
+
+
+# ---- diagonal ops (csrc/diag.hip) ------------------------------------------------
+
+def _row_bytes(x: torch.Tensor) -> int:
+    b = x.element_size()
+    for s in x.shape[1:]:
+        b *= s
+    return b
+
+
+def diag_extent(M: int, N: int, k: int) -> Tuple[int, int]:
+    """(start, num_diag) of the k-th diagonal of an M x N matrix: its cells are (r, r + k)
+    for r in [start, start + num_diag)."""
+    n = min(M, N - k) if k >= 0 else min(M + k, N)
+    return max(-k, 0), max(n, 0)
+
+
+class DiagPlan:
+    """What psa_diag_count left behind for psa_diag_write: the result's row pointer and
+    row lengths (its caches), the adjusted column counts, and the workspace."""
+
+    def __init__(self, M, N, k, insert, nnz, rowcount, rowptr, colcount, nnz_out, ws):
+        self.M, self.N, self.k, self.insert, self.nnz = M, N, k, insert, nnz
+        self.rowcount, self.rowptr, self.colcount, self.nnz_out, self.ws = rowcount, rowptr, colcount, nnz_out, ws
+
+
+def diag_count(rowptr: torch.Tensor, col: torch.Tensor, M: int, N: int, k: int, insert: bool,
+               colcount: Optional[torch.Tensor] = None) -> DiagPlan:
+    """Count pass of remove_diag (insert=False) / set_diag (insert=True) and the one host
+    read: the output size rowptr'[M]."""
+    rowptr, col = _index(rowptr, "rowptr"), _index(col, "col")
+    if rowptr.numel() != M + 1:
+        raise ValueError("rowptr must have M + 1 entries")
+    if colcount is not None:
+        colcount = _index(colcount, "colcount")
+    dev = rowptr.device
+    lib = _lib.load()
+    rowcount = torch.empty(M, dtype=torch.int64, device=dev)
+    rowptr_out = torch.empty(M + 1, dtype=torch.int64, device=dev)
+    colcount_out = torch.empty(N, dtype=torch.int64, device=dev) if colcount is not None else None
+    ws = _workspace(lib.psa_diag_workspace_bytes(M), dev)
+    with _on(dev):
+        check(lib.psa_diag_count(_ptr(rowptr), _ptr(col), M, N, int(k), int(bool(insert)), _ptr(colcount),
+                                 _ptr(rowcount), _ptr(rowptr_out), _ptr(colcount_out), _ptr(ws), ws.numel(),
+                                 _stream()))
+        nnz_out = int(rowptr_out[M].item())
+    return DiagPlan(M, N, int(k), bool(insert), col.numel(), rowcount, rowptr_out, colcount_out, nnz_out, ws)
+
+
+def diag_write(plan: DiagPlan, rowptr: torch.Tensor, col: torch.Tensor, value: Optional[torch.Tensor],
+               diag_values: Optional[torch.Tensor] = None, want_maps: bool = False):
+    """Write pass: (col', value' or None, out_pos or None, diag_pos or None).  diag_values:
+    [num_diag, *value.shape[1:]] of value's dtype (insert plans with values)."""
+    rowptr, col = _index(rowptr, "rowptr"), _index(col, "col")
+    dev = rowptr.device
+    col_out = torch.empty(plan.nnz_out, dtype=torch.int64, device=dev)
+    value_out = rb = None
+    if value is not None:
+        _gpu(value, "value")
+        value = value.contiguous()
+        rb = _row_bytes(value)
+        value_out = torch.empty((plan.nnz_out,) + tuple(value.shape[1:]), dtype=value.dtype, device=dev)
+        if plan.insert:
+            if diag_values is None:
+                raise ValueError("diag_values required to insert into a matrix with values")
+            _gpu(diag_values, "diag_values")
+            if (diag_values.dtype != value.dtype or diag_values.shape[1:] != value.shape[1:]
+                    or diag_values.shape[0] != diag_extent(plan.M, plan.N, plan.k)[1]):
+                raise ValueError("diag_values must be [num_diag, *value.shape[1:]] of value's dtype")
+            diag_values = diag_values.contiguous()
+    if value is None or not plan.insert:
+        diag_values = None
+    out_pos = diag_pos = None
+    if want_maps:
+        out_pos = torch.empty(plan.nnz, dtype=torch.int64, device=dev)
+        if diag_values is not None:
+            diag_pos = torch.empty(diag_values.shape[0], dtype=torch.int64, device=dev)
+    with _on(dev):
+        check(_lib.load().psa_diag_write(_ptr(rowptr), _ptr(col), _ptr(value), rb or 0, _ptr(diag_values),
+                                         plan.M, plan.N, plan.k, int(plan.insert), plan.nnz, _ptr(plan.rowptr),
+                                         plan.nnz_out, _ptr(plan.ws), _ptr(col_out), _ptr(value_out),
+                                         _ptr(out_pos), _ptr(diag_pos), _stream()))
+    return col_out, value_out, out_pos, diag_pos
+
+
+def get_diag(rowptr: torch.Tensor, col: torch.Tensor, value: Optional[torch.Tensor], M: int, N: int,
+             want_pos: bool = False):
+    """(main diagonal [min(M, N), *value.shape[1:]], positions of the entries read or None).
+    Value-less: float32 ones where an entry is stored."""
+    rowptr, col = _index(rowptr, "rowptr"), _index(col, "col")
+    dev = rowptr.device
+    D = min(M, N)
+    if value is not None:
+        _gpu(value, "value")
+        value = value.contiguous()
+        if value.numel() == 0:  # no entries (or zero-width rows): nothing is stored on the diagonal
+            pos = torch.full((D,), -1, dtype=torch.int64, device=dev) if want_pos else None
+            return torch.zeros((D,) + tuple(value.shape[1:]), dtype=value.dtype, device=dev), pos
+        out = torch.empty((D,) + tuple(value.shape[1:]), dtype=value.dtype, device=dev)
+    else:
+        out = torch.empty(D, dtype=torch.float32, device=dev)
+    pos = torch.empty(D, dtype=torch.int64, device=dev) if want_pos else None
+    with _on(dev):
+        check(_lib.load().psa_get_diag(_ptr(rowptr), _ptr(col), _ptr(value), _row_bytes(value) if value is not None
+                                       else 0, M, N, _ptr(out), _ptr(pos), _stream()))
+    return out, pos
+
+
+def diag_gather(src: torch.Tensor, index_map: torch.Tensor) -> torch.Tensor:
+    """src[index_map] with zero rows where index_map is -1."""
+    _gpu(src, "src")
+    index_map = _index(index_map, "map")
+    src = src.contiguous()
+    out = torch.empty((index_map.numel(),) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    with _on(src.device):
+        check(_lib.load().psa_diag_gather(_ptr(src), _ptr(index_map), index_map.numel(), _row_bytes(src),
+                                          _ptr(out), _stream()))
+    return out
+
+
+def diag_scatter(src: torch.Tensor, pos: torch.Tensor, n: int) -> torch.Tensor:
+    """zeros([n, *src.shape[1:]]) with row pos[i] = src[i] for pos[i] >= 0."""
+    _gpu(src, "src")
+    pos = _index(pos, "pos")
+    src = src.contiguous()
+    out = torch.zeros((n,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    with _on(src.device):
+        check(_lib.load().psa_diag_scatter(_ptr(src), _ptr(pos), pos.numel(), _row_bytes(src), _ptr(out),
+                                           _stream()))
+    return out
