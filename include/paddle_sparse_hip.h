@@ -834,6 +834,44 @@ int psa_diag_gather(const void* src, const int64_t* map, int64_t n, int64_t row_
 int psa_diag_scatter(const void* src, const int64_t* pos, int64_t n, int64_t row_bytes, void* out,
                      psa_stream_t stream);
 
+/* ---- GraphSAINT random-walk sampler (torch_sparse rw.py / saint.py) on a SQUARE N x N
+ * sorted CSR matrix (rowptr int64[N+1], col int64[nnz]).
+ *
+ * random_walk: out int64[S, walk_length + 1], row n = the walk from start[n] (int64[S]):
+ * out[n, 0] = start[n]; at step l (0-based) from node c with d = rowptr[c+1] - rowptr[c]
+ * entries, the next node is col[rowptr[c] + randint(seed, n, l, d)] when d > 0 and c
+ * itself when d == 0 (a walk stays at a node without entries).  randint is the draw of
+ * psa_sample_select (stream n, draw l), so step 0 of walk n picks the edge
+ * psa_sample_select picks for subset row n with num_neighbors = 1, replace = 1.  Duplicate
+ * entries are separate choices.  flags: int64[1], zeroed by the caller; bit 0 is set when a
+ * start lies outside [0, N) (that walk's row is then left unwritten).  One launch, no
+ * atomics on the output; deterministic. */
+int psa_random_walk(const int64_t* rowptr, const int64_t* col, int64_t N, const int64_t* start, int64_t S,
+                    int64_t walk_length, uint64_t seed, int64_t* out, int64_t* flags, psa_stream_t stream);
+/* Test/bench hook: the store scheme of psa_random_walk for this process (0 = default =
+ * 2; 1 = one 8-byte store per step, 2 = bursts of 16 steps held in registers, 3 / 4 =
+ * 1 / 2 with two walks per lane).  Returns the previous value.  All produce the same bits. */
+int psa_random_walk_set_variant(int variant);
+
+/* saint_subgraph: the subgraph induced by node_idx (int64[S], any order, duplicates
+ * allowed).  assoc[node_idx[i]] = i (the last duplicate wins); for every i in order and
+ * every entry e of row node_idx[i] with assoc[col[e]] >= 0, the candidate order emits
+ * (row' = i, col' = assoc[col[e]], edge = e).  Two calls and ONE host read:
+ *   psa_saint_count(...)   info int64[2] = {nnz', flags} on the device: the host read
+ *   psa_saint_write(...)   row_out, col_out, edge_out int64[nnz'] in candidate order,
+ *                          rowptr_out int64[S+1]
+ * flags: bit 0 = a node_idx entry outside [0, N) (the output is then meaningless), bit 1 =
+ * node_idx has duplicates, bit 2 = node_idx decreases somewhere.  Without bit 2 the
+ * candidate order is sorted by (row', col'); with it the caller re-sorts (stable) by
+ * (row', col').  workspace: psa_saint_workspace_bytes(S, N) bytes, 16-byte aligned, kept
+ * between the two calls.  Deterministic; hub rows are split across workgroups. */
+size_t psa_saint_workspace_bytes(int64_t S, int64_t N);
+int psa_saint_count(const int64_t* rowptr, const int64_t* col, int64_t N, const int64_t* node_idx, int64_t S,
+                    void* workspace, size_t workspace_bytes, int64_t* info, psa_stream_t stream);
+int psa_saint_write(const int64_t* rowptr, const int64_t* col, int64_t N, const int64_t* node_idx, int64_t S,
+                    const void* workspace, int64_t nnz_out, int64_t* rowptr_out, int64_t* row_out,
+                    int64_t* col_out, int64_t* edge_out, psa_stream_t stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

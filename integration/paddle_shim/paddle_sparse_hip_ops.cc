@@ -993,3 +993,79 @@ PD_BUILD_OP(get_diag)
     .Outputs({"out"})
     .Attrs({"n: int64_t"})
     .SetKernelFn(PD_KERNEL(get_diag));
+
+// ---- random_walk / saint_subgraph (seam: torch_sparse/rw.py and saint.py, paddle_sparse_amd/rw.py and saint.py) ----
+// random_walk: out int64[S, walk_length + 1] from psa_random_walk; a start outside the square matrix
+// throws (one 8-byte host read of the kernel's flag).  `seed` comes from Paddle's default generator,
+// as for sample_adj.
+std::vector<paddle::Tensor> random_walk(paddle::Tensor& rowptr, paddle::Tensor& col, paddle::Tensor& start,
+                                        int64_t walk_length) {
+  CHECK_GPU(rowptr);
+  CHECK_GPU(start);
+  CHECK_I64(rowptr);
+  CHECK_I64(col);
+  CHECK_I64(start);
+  PD_CHECK(start.shape().size() == 1, "start must be 1-D");
+  PD_CHECK(walk_length >= 0, "walk_length must be >= 0");
+  const auto place = rowptr.place();
+  const int64_t S = start.numel(), n = rowptr.numel() - 1;
+  const uint64_t seed = static_cast<uint64_t>(
+      paddle::experimental::randint(0, INT64_MAX, {1}, paddle::DataType::INT64, paddle::CPUPlace()).data<int64_t>()[0]);
+  auto out = paddle::empty({S, walk_length + 1}, paddle::DataType::INT64, place);
+  if (S == 0) return {out};
+  auto flags = paddle::full({1}, 0, paddle::DataType::INT64, place);
+  PSA_CALL(psa_random_walk(i64(rowptr), i64(col), n, i64(start), S, walk_length, seed, out.data<int64_t>(),
+                           flags.data<int64_t>(), stream_of(rowptr)));
+  PD_CHECK((read_i64(flags, 0, 1)[0] & 1) == 0, "random_walk: a start node lies outside the matrix");
+  return {out};
+}
+PD_BUILD_OP(random_walk)
+    .Inputs({"rowptr", "col", "start"})
+    .Outputs({"out"})
+    .Attrs({"walk_length: int64_t"})
+    .SetKernelFn(PD_KERNEL(random_walk));
+
+// saint_subgraph: psa_saint_count -> one host read ({nnz', flags}) -> psa_saint_write; when node_idx
+// decreases somewhere (flag bit 2), one stable sort of row' * S + col' puts the columns in order.
+// Outputs rowptr', row', col' and edge_index (the values are value[edge_index], a gather the seam does).
+std::vector<paddle::Tensor> saint_subgraph(paddle::Tensor& rowptr, paddle::Tensor& col, paddle::Tensor& node_idx) {
+  CHECK_GPU(rowptr);
+  CHECK_GPU(node_idx);
+  CHECK_I64(rowptr);
+  CHECK_I64(col);
+  CHECK_I64(node_idx);
+  PD_CHECK(node_idx.shape().size() == 1, "node_idx must be 1-D");
+  void* s = stream_of(rowptr);
+  const auto place = rowptr.place();
+  const int64_t S = node_idx.numel(), n = rowptr.numel() - 1;
+  const size_t ws_bytes = psa_saint_workspace_bytes(S, n);
+  auto ws = scratch(ws_bytes, place);
+  auto info = i64_empty(2, place);
+  PSA_CALL(psa_saint_count(i64(rowptr), i64(col), n, i64(node_idx), S, ws.data<uint8_t>(), ws_bytes,
+                           info.data<int64_t>(), s));
+  const auto host = read_i64(info, 0, 2);  // the one host read
+  const int64_t nnz_out = host[0], flags = host[1];
+  PD_CHECK((flags & 1) == 0, "saint_subgraph: a node lies outside the matrix");
+  auto rowptr_out = i64_empty(S + 1, place), row_out = i64_empty(nnz_out, place);
+  auto col_out = i64_empty(nnz_out, place), edge_out = i64_empty(nnz_out, place);
+  PSA_CALL(psa_saint_write(i64(rowptr), i64(col), n, i64(node_idx), S, ws.data<uint8_t>(), nnz_out,
+                           rowptr_out.data<int64_t>(), row_out.data<int64_t>(), col_out.data<int64_t>(),
+                           edge_out.data<int64_t>(), s));
+  if ((flags & 4) == 0 || nnz_out == 0) return {rowptr_out, row_out, col_out, edge_out};
+  auto keys = i64_empty(nnz_out, place), sorted = i64_empty(nnz_out, place), perm = i64_empty(nnz_out, place);
+  auto col_sorted = i64_empty(nnz_out, place), edge_sorted = i64_empty(nnz_out, place);
+  PSA_CALL(psa_make_keys(i64(row_out), i64(col_out), S, nnz_out, keys.data<int64_t>(), nullptr, s));
+  const int64_t max_key = S * S;
+  const size_t sort_bytes = psa_index_sort_workspace_bytes(nnz_out, max_key);
+  auto sort_ws = scratch(sort_bytes, place);
+  PSA_CALL(psa_index_sort(i64(keys), nnz_out, max_key, sorted.data<int64_t>(), perm.data<int64_t>(),
+                          sort_ws.data<uint8_t>(), sort_bytes, s));
+  PSA_SORT_OK(sort_ws.data<uint8_t>(), nnz_out, max_key, s);
+  PSA_CALL(psa_split_keys(i64(sorted), nnz_out, S, nullptr, col_sorted.data<int64_t>(), s));
+  PSA_CALL(psa_gather_rows(edge_out.data<int64_t>(), i64(perm), nnz_out, 8, edge_sorted.data<int64_t>(), s));
+  return {rowptr_out, row_out, col_sorted, edge_sorted};
+}
+PD_BUILD_OP(saint_subgraph)
+    .Inputs({"rowptr", "col", "node_idx"})
+    .Outputs({"rowptr_out", "row_out", "col_out", "edge_index"})
+    .SetKernelFn(PD_KERNEL(saint_subgraph));

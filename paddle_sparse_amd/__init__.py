@@ -61,6 +61,8 @@ if not _running_the_builder():
         ("matmul", ("spmm", "matmul")),
         ("spspmm", ("spspmm",)),
         ("diag", ("remove_diag", "set_diag", "fill_diag", "get_diag")),
+        ("rw", ("random_walk",)),
+        ("saint", ("saint_subgraph",)),
     )
 
     __all__ = ["__version__"]

@@ -146,6 +146,14 @@ SIGNATURES = {
     "psa_get_diag": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "psa_diag_gather": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "psa_diag_scatter": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "psa_random_walk": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_uint64, c_void_p,
+                                c_void_p, c_void_p]),
+    "psa_random_walk_set_variant": (c_int, [c_int]),
+    "psa_saint_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "psa_saint_count": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_size_t, c_void_p,
+                                c_void_p]),
+    "psa_saint_write": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

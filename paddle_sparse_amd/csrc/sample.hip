@@ -15,29 +15,19 @@
 //   n_id, keys  a scan of the flags IS the first-seen numbering; keys =
 //               i * n_out + new column id, sorted (stable) by the caller
 //
-// Random picks use a counter-based generator: draw t of subset row i depends on
+// Random picks use the counter-based generator of rng.h: draw t of subset row i depends on
 // (seed, i, t) only, so results do not depend on scheduling and the CPU oracle
 // reproduces them bit for bit.  (The reference draws from Paddle's global
 // generator, which no other implementation can reproduce.)
 #include "common.h"
+#include "rng.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int64_t kUnseen = INT64_MIN;
 
-__host__ __device__ inline uint64_t mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// uniform integer in [0, n): high half of a 64 x 64 product (n > 0)
-__device__ inline int64_t randint(uint64_t seed, int64_t i, int64_t t, int64_t n) {
-  const uint64_t r = mix64(mix64(seed ^ mix64(static_cast<uint64_t>(i))) + static_cast<uint64_t>(t));
-  return static_cast<int64_t>(__umul64hi(r, static_cast<uint64_t>(n)));
-}
+using psa::randint;
 
 __device__ inline int64_t picks_of(int64_t deg, int64_t k, int replace) {
   if (k < 0) return deg;                       // sample_cpu.cpp:45-63

@@ -1494,3 +1494,62 @@ def diag_scatter(src: torch.Tensor, pos: torch.Tensor, n: int) -> torch.Tensor:
         check(_lib.load().psa_diag_scatter(_ptr(src), _ptr(pos), pos.numel(), _row_bytes(src), _ptr(out),
                                            _stream()))
     return out
+
+
+# ---- GraphSAINT random-walk sampler (csrc/walk.hip) --------------------------------
+
+def random_walk(rowptr: torch.Tensor, col: torch.Tensor, start: torch.Tensor, walk_length: int,
+                seed: int) -> torch.Tensor:
+    """int64[S, walk_length + 1] walks of a square CSR matrix from start (int64[S]): the
+    next node is a uniform draw among the current node's entries (the counter-based
+    stream of sample_adj: walk n, step l), or the node itself when it has none.  Raises
+    IndexError when a start lies outside the matrix (one host read)."""
+    rowptr, col, start = _index(rowptr, "rowptr"), _index(col, "col"), _index(start, "start")
+    L = int(walk_length)
+    if L < 0:
+        raise ValueError("walk_length must be >= 0")
+    N, S, dev = rowptr.numel() - 1, start.numel(), rowptr.device
+    out = torch.empty((S, L + 1), dtype=torch.int64, device=dev)
+    if S == 0:
+        return out
+    flags = torch.zeros(1, dtype=torch.int64, device=dev)
+    with _on(dev):
+        check(_lib.load().psa_random_walk(_ptr(rowptr), _ptr(col), N, _ptr(start), S, L, int(seed) & (2**64 - 1),
+                                          _ptr(out), _ptr(flags), _stream()))
+        if int(flags.item()) & 1:
+            raise IndexError(f"random_walk: a start node lies outside [0, {N})")
+    return out
+
+
+def random_walk_set_variant(variant: int) -> int:
+    """Bench hook: the store scheme of psa_random_walk (0 = default); returns the previous one."""
+    return _lib.load().psa_random_walk_set_variant(int(variant))
+
+
+SAINT_DUPLICATES, SAINT_UNSORTED = 2, 4
+
+
+def saint_subgraph(rowptr: torch.Tensor, col: torch.Tensor, node_idx: torch.Tensor):
+    """The subgraph of a square CSR matrix induced by node_idx (int64[S]): returns
+    (rowptr' int64[S+1], row', col', edge_index int64[nnz'], flags) in candidate order
+    (selection order of the rows, storage order inside a row); col' = position of the
+    column's node in node_idx, the last one for a duplicated node.  flags has
+    SAINT_DUPLICATES when node_idx repeats a node and SAINT_UNSORTED when it decreases
+    somewhere (only then is candidate order not sorted by (row', col')).  Two C-ABI calls
+    and ONE host read; IndexError for a node outside the matrix."""
+    rowptr, col, node_idx = _index(rowptr, "rowptr"), _index(col, "col"), _index(node_idx, "node_idx")
+    N, S, dev = rowptr.numel() - 1, node_idx.numel(), rowptr.device
+    lib = _lib.load()
+    ws = _workspace(lib.psa_saint_workspace_bytes(S, N), dev)
+    info = torch.empty(2, dtype=torch.int64, device=dev)
+    with _on(dev):
+        check(lib.psa_saint_count(_ptr(rowptr), _ptr(col), N, _ptr(node_idx), S, _ptr(ws), ws.numel(), _ptr(info),
+                                  _stream()))
+        nnz_out, flags = info.tolist()  # the one host read
+        if flags & 1:
+            raise IndexError(f"saint_subgraph: a node lies outside [0, {N})")
+        rowptr_out = torch.empty(S + 1, dtype=torch.int64, device=dev)
+        out = torch.empty((3, nnz_out), dtype=torch.int64, device=dev)
+        check(lib.psa_saint_write(_ptr(rowptr), _ptr(col), N, _ptr(node_idx), S, _ptr(ws), nnz_out,
+                                  _ptr(rowptr_out), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()))
+    return rowptr_out, out[0], out[1], out[2], flags
