@@ -533,7 +533,11 @@ int psa_coalesce_small(const int64_t* row, const int64_t* col, int64_t n,
  * psa_unique_* and psa_segment_reduce.  transpose(index, value, m, n)
  * (paddle_sparse/transpose.py:41-65) is the same two calls with row/col and M/N
  * swapped.  workspace: psa_coalesce_workspace_bytes(n, M, N) bytes, 16-byte
- * aligned, untouched between the two calls. */
+ * aligned, untouched between the two calls.
+ * Non-finite values (every form of the chain, psa_coalesce_small_fused included):
+ * min / max give NaN for an entry whose duplicates hold one, at any position; sum /
+ * mean are IEEE (+inf and -inf together give NaN); the sign of a zero min / max on
+ * a +0 / -0 tie is unspecified. */
 size_t psa_coalesce_workspace_bytes(int64_t n, int64_t M, int64_t N);
 int psa_coalesce_count(const int64_t* row, const int64_t* col, const void* value,
                        int dtype, int64_t D, int64_t n, int64_t M, int64_t N,
@@ -684,7 +688,8 @@ int psa_unique_write(const int64_t* sorted_keys, int64_t n, int64_t N,
  * of equal keys, taken sequentially in run order (psa_segment_reduce's order and bits).  The thread that
  * writes a pair reduces its run: meant for inputs whose runs are short (count * 32 > n); a heavily
  * duplicated input is better served by psa_unique_write + psa_segment_reduce, whose reducer then takes a
- * wave per run.  Other dtypes: PSA_ERR_UNSUPPORTED. */
+ * wave per run.  Other dtypes: PSA_ERR_UNSUPPORTED.  Non-finite values as psa_segment_reduce: NaN
+ * propagates through min / max from any position of a run, sum / mean are IEEE. */
 int psa_unique_write_reduce(int reduce, int dtype, const int64_t* sorted_keys, int64_t n, int64_t N,
                             const void* workspace, const int64_t* count, int64_t* index_out,
                             const void* payload, void* value_out, psa_stream_t stream);
@@ -696,7 +701,11 @@ int psa_unique_write_reduce(int reduce, int dtype, const int64_t* sorted_keys, i
  * tensor.py:437.  Semantics = pytorch_scatter segment_csr: empty segment ->
  * 0, mean = sum / count (floor division for integer dtypes), min/max values
  * only.  Sums run in segment order.  n_hint = ptr[nseg] if known (selects the
- * wave-per-segment kernel for long segments), else 0. */
+ * wave-per-segment kernel for long segments), else 0.
+ * Non-finite values, whichever kernel runs: min / max give NaN for a segment
+ * that holds a NaN in that column, at any position; sum / mean are IEEE (+inf
+ * and -inf in one segment give NaN); an empty segment gives 0; the sign of a
+ * zero min / max on a +0 / -0 tie is unspecified. */
 int psa_segment_reduce(int reduce, int dtype, const void* src,
                        const int64_t* perm, const int64_t* ptr, int64_t nseg,
                        int64_t D, int64_t n_hint, void* out,
@@ -707,7 +716,11 @@ int psa_segment_reduce(int reduce, int dtype, const void* src,
  * paddle_scatter.scatter at reduce.py:40-42 (reduce over dim 0, index = col).
  * Rows no index points at are 0; mean = sum / count (floor for integers).
  * workspace (psa_scatter_workspace_bytes(dim_size) bytes) is needed for
- * mean/min/max.  Float sums use atomics: order not fixed. */
+ * mean/min/max.  Float sums use atomics: order not fixed.
+ * Non-finite values: min / max give NaN for a row that receives one (the float
+ * min / max atomics drop NaN; a pass of plain stores after them writes it); sum /
+ * mean are IEEE; a row nothing points at gives 0 whatever the reduction; the
+ * sign of a zero min / max on a +0 / -0 tie is unspecified. */
 size_t psa_scatter_workspace_bytes(int64_t dim_size);
 int psa_scatter_reduce(int reduce, int dtype, const void* src,
                        const int64_t* index, int64_t n, int64_t D,

@@ -31,6 +31,7 @@ using psa::Acc;
 using psa::digit_of;
 using psa::kRadix;
 using psa::mean_div;
+using psa::minmax_step;
 using psa::wave_match;
 using psa::wave_rank;
 
@@ -221,7 +222,7 @@ small_coalesce_sort_kernel(const int64_t* __restrict__ row, const int64_t* __res
         float acc = v[lidx[b]];
         for (uint32_t j = b + 1; j < e; ++j) {
           const float x = v[lidx[j]];
-          acc = red == R_MIN ? (x < acc ? x : acc) : red == R_MAX ? (x > acc ? x : acc) : acc + x;
+          acc = red == R_MIN ? minmax_step<true>(x, acc) : red == R_MAX ? minmax_step<false>(x, acc) : acc + x;
         }
         if (red == R_MEAN) acc = acc / static_cast<float>(e - b);
         static_cast<float*>(value_out)[o] = acc;
@@ -230,7 +231,7 @@ small_coalesce_sort_kernel(const int64_t* __restrict__ row, const int64_t* __res
         int32_t acc = v[lidx[b]];
         for (uint32_t j = b + 1; j < e; ++j) {
           const int32_t x = v[lidx[j]];
-          acc = red == R_MIN ? (x < acc ? x : acc) : red == R_MAX ? (x > acc ? x : acc) : acc + x;
+          acc = red == R_MIN ? minmax_step<true>(x, acc) : red == R_MAX ? minmax_step<false>(x, acc) : acc + x;
         }
         if (red == R_MEAN) acc = mean_div<int32_t>(acc, static_cast<int64_t>(e - b));
         static_cast<int32_t*>(value_out)[o] = acc;
@@ -290,8 +291,8 @@ small_pack_reduce_kernel(const int64_t* __restrict__ row_c, const int64_t* __res
   A acc = Acc<T>::load(value + perm[b] * D + d);
   for (int64_t i = b + 1; i < e; ++i) {
     const A x = Acc<T>::load(value + perm[i] * D + d);
-    if (RED == R_MIN) acc = x < acc ? x : acc;
-    else if (RED == R_MAX) acc = x > acc ? x : acc;
+    if (RED == R_MIN) acc = minmax_step<true>(x, acc);
+    else if (RED == R_MAX) acc = minmax_step<false>(x, acc);
     else acc = acc + x;
   }
   if (RED == R_MEAN) acc = mean_div<A>(acc, e - b);

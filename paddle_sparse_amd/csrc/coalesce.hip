@@ -23,6 +23,7 @@ namespace {
 
 using psa::Acc;
 using psa::mean_div;
+using psa::minmax_step;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
@@ -188,8 +189,8 @@ segment_reduce_kernel(const T* __restrict__ src, const int64_t* __restrict__ per
     acc = Acc<T>::load(src + (perm ? perm[b] : b) * D + d);
     for (int64_t i = b + 1; i < e; ++i) {
       const A x = Acc<T>::load(src + (perm ? perm[i] : i) * D + d);
-      if (RED == R_MIN) acc = x < acc ? x : acc;
-      else if (RED == R_MAX) acc = x > acc ? x : acc;
+      if (RED == R_MIN) acc = minmax_step<true>(x, acc);
+      else if (RED == R_MAX) acc = minmax_step<false>(x, acc);
       else acc = acc + x;
     }
     if (RED == R_MEAN) acc = mean_div<A>(acc, e - b);
@@ -241,8 +242,8 @@ unique_write_reduce_kernel(const int64_t* __restrict__ keys, int64_t n, int64_t 
       int64_t k = i + 1;
       while (k < n && keys[k] == key[j]) {
         const A x = Acc<T>::load(payload + k);
-        if (RED == R_MIN) acc = x < acc ? x : acc;
-        else if (RED == R_MAX) acc = x > acc ? x : acc;
+        if (RED == R_MIN) acc = minmax_step<true>(x, acc);
+        else if (RED == R_MAX) acc = minmax_step<false>(x, acc);
         else acc = acc + x;
         ++k;
       }
@@ -275,9 +276,9 @@ segment_reduce_wave_kernel(const T* __restrict__ src,
       acc = x;
       has = true;
     } else if (RED == R_MIN) {
-      acc = x < acc ? x : acc;
+      acc = minmax_step<true>(x, acc);
     } else if (RED == R_MAX) {
-      acc = x > acc ? x : acc;
+      acc = minmax_step<false>(x, acc);
     } else {
       acc = acc + x;
     }
@@ -288,8 +289,8 @@ segment_reduce_wave_kernel(const T* __restrict__ src,
     const bool ohas = __shfl_xor(static_cast<int>(has), off);
     if (ohas) {
       if (!has) acc = o;
-      else if (RED == R_MIN) acc = o < acc ? o : acc;
-      else if (RED == R_MAX) acc = o > acc ? o : acc;
+      else if (RED == R_MIN) acc = minmax_step<true>(o, acc);
+      else if (RED == R_MAX) acc = minmax_step<false>(o, acc);
       else acc = acc + o;
       has = true;
     }

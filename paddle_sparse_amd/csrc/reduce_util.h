@@ -1,5 +1,5 @@
-// Accumulator types and the mean division of the segmented reducers
-// (coalesce.hip, chain.hip).
+// Accumulator types, the min / max step and the mean division of the segmented
+// reducers (coalesce.hip, chain.hip).
 #pragma once
 
 #include <hip/hip_bf16.h>
@@ -38,6 +38,20 @@ __device__ __forceinline__ A mean_div(A acc, int64_t cnt) {
     return q;
   } else {
     return acc / static_cast<A>(cnt);
+  }
+}
+
+// One min / max step of every reducer: the better of the running value `acc` and the next entry `x`.
+// Floating accumulators propagate NaN whatever its position in the group (numpy / torch amin, amax and
+// the oracle do): a NaN `x` is taken, and a NaN `acc` stays because it fails every ordered compare.
+// Integer accumulators are the plain compare-and-select.
+template <bool MIN, typename A>
+__device__ __forceinline__ A minmax_step(A x, A acc) {
+  const bool better = MIN ? x < acc : x > acc;
+  if constexpr (std::is_floating_point<A>::value) {
+    return (better || x != x) ? x : acc;
+  } else {
+    return better ? x : acc;
   }
 }
 

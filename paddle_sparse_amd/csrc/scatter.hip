@@ -4,6 +4,8 @@
 // (SparseTensor.sum/mean/min/max(dim=0): values scattered by `col`).
 // Semantics = pytorch_scatter: untouched rows -> 0, mean = sum / count
 // (floor division for integer dtypes), min/max return values only.
+// Non-finite values: sum / mean are IEEE; min / max give NaN for a group that holds
+// one (the hardware float min / max atomics drop NaN, so a pass of its own stores it).
 // Atomics: one element per lane, consecutive lanes on consecutive elements of
 // a row, so a wave instruction covers whole 256-B runs whenever D >= 64.
 #include <type_traits>
@@ -68,6 +70,25 @@ scatter_kernel(const T* __restrict__ src, const int64_t* __restrict__ index,
   if (count && d == 0) atomicAdd(count + r, 1u);
 }
 
+// Float min / max, after the atomic pass: the hardware atomics return the non-NaN operand, so a
+// NaN source never reaches its destination through them.  Every NaN source stores the one quiet
+// NaN over its destination here: a plain vector store, every writer of a word writes the same bits,
+// and no atomic runs any more, so nothing can undo it.  Finite data only pays the read of `src`.
+template <typename T>
+__global__ void __launch_bounds__(kThreads)
+scatter_nan_kernel(const T* __restrict__ src, const int64_t* __restrict__ index, int64_t n, int64_t D,
+                   int64_t dim_size, T* __restrict__ out) {
+  const int64_t g = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  if (g >= n * D) return;
+  const T x = src[g];
+  if (x == x) return;
+  const int64_t i = D == 1 ? g : g / D;
+  const int64_t d = D == 1 ? 0 : g - i * D;
+  const int64_t r = index[i];
+  if (r < 0 || r >= dim_size) return;  // never store out of bounds
+  out[r * D + d] = static_cast<T>(__builtin_nanf(""));
+}
+
 template <typename T, int RED>
 __global__ void __launch_bounds__(kThreads)
 scatter_finish_kernel(T* __restrict__ out, const unsigned int* __restrict__ count,
@@ -104,6 +125,10 @@ int run(const void* src, const int64_t* index, int64_t n, int64_t D,
     hipLaunchKernelGGL((scatter_kernel<T, RED>), dim3(static_cast<unsigned>(nb)),
                        dim3(kThreads), 0, s, static_cast<const T*>(src), index, n,
                        D, dim_size, o, RED == R_SUM ? nullptr : count);
+    if constexpr (std::is_floating_point<T>::value && (RED == R_MIN || RED == R_MAX)) {
+      hipLaunchKernelGGL((scatter_nan_kernel<T>), dim3(static_cast<unsigned>(nb)), dim3(kThreads), 0, s,
+                         static_cast<const T*>(src), index, n, D, dim_size, o);
+    }
   }
   if (RED != R_SUM) {
     hipLaunchKernelGGL((scatter_finish_kernel<T, RED>), dim3(static_cast<unsigned>(ob)),

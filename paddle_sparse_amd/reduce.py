@@ -15,6 +15,11 @@ from . import ops
 from .storage import _SORT_BEATS_ATOMICS
 from .tensor import SparseTensor
 
+# fp16 / bf16 values reduce over dim 0 by CSC segments at every size: the segmented reducer accumulates
+# them in fp32 and rounds once, where a scatter would round after every 16-bit atomic (and in an order
+# that changes from run to run)
+_SEGMENTS_ONLY = (torch.float16, torch.bfloat16)
+
 _DENSE = {"sum": "sum", "add": "sum", "mean": "mean", "min": "amin", "max": "amax"}
 
 
@@ -39,7 +44,8 @@ def reduction(src: SparseTensor, dim: Optional[int] = None, reduce: str = "sum")
     if dim == 0:
         if value is not None:
             st = src.storage
-            if (st.has_csr2csc() and st.has_colptr()) or st.col().numel() >= _SORT_BEATS_ATOMICS:
+            if ((st.has_csr2csc() and st.has_colptr()) or st.col().numel() >= _SORT_BEATS_ATOMICS
+                    or value.dtype in _SEGMENTS_ONLY):
                 # Same sums as the scatter of reduce.py:42, taken column by
                 # column in CSC order: no atomics (scattered device atomics
                 # run ~20 G/s on this chip), and reproducible bit for bit.

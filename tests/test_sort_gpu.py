@@ -249,7 +249,8 @@ def test_segment_csr_long_segments_wave_kernel(reduce):
     indptr = np.concatenate([[0], cuts, [n]]).astype(np.int64)
     got = ops.segment_csr(dev(src), dev(indptr), reduce).cpu().numpy()
     ref = so.segment_csr_fast(src, indptr, reduce)
-    np.testing.assert_allclose(got, ref, rtol=1e-6, atol=0)
+    # integer data, sums far below 2^24: any summation order gives the same fp32 bits
+    assert np.array_equal(got, ref)
 
 
 def test_count_read_brings_back_the_sorts_lookback_diagnostic():
