@@ -64,6 +64,11 @@ def index_select(src: SparseTensor, dim: int, idx: torch.Tensor) -> SparseTensor
 
 
 def index_select_nnz(src: SparseTensor, idx: torch.Tensor, layout: Optional[str] = None) -> SparseTensor:
+    """index_select.py:83-101: the stored entries idx[0], idx[1], ... (positions in `layout` order).  The
+    result is marked sorted without a check, as in the reference: it is a valid storage when the selected
+    entries come out in (row, col) order — an ascending `idx` in coo layout.  For any other selection the
+    entries and values are still the selected ones, in the order given, but every cache and reduction derived
+    from the result is unspecified."""
     assert idx.dim() == 1
     idx = idx.to(torch.int64).contiguous()
     if get_layout(layout) == "csc":
@@ -89,6 +94,8 @@ def masked_select(src: SparseTensor, dim: int, mask: torch.Tensor) -> SparseTens
 
 
 def masked_select_nnz(src: SparseTensor, mask: torch.Tensor, layout: Optional[str] = None) -> SparseTensor:
+    """masked_select.py:80-96: the stored entries whose mask bit (one per entry, in `layout` order) is set, in
+    storage order — always a sorted storage."""
     assert mask.dim() == 1
     if get_layout(layout) == "csc":
         mask = ops.gather_rows(mask.to(torch.uint8), src.storage.csc2csr()).to(torch.bool)

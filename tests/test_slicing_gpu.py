@@ -103,19 +103,27 @@ def test_index_select_nnz(mat):
 
 # ---- against the oracle's restatement of index_select.py / masked_select.py / narrow.py -------------
 
-def _same(t, ref, caches=None):
-    """Same entries, order, values and sizes as the oracle's Storage; caches the reference
-    passes to the new SparseStorage hold the same numbers here whenever they are present."""
+_CACHES = ("rowcount", "colptr", "colcount", "csr2csc", "csc2csr")
+
+
+def _same(t, ref, caches=None, expect_present=()):
+    """Same entries, order, values and sizes as the oracle's Storage.  `expect_present`: exactly these caches are
+    present on the result, and each of them that the reference passes to the new SparseStorage holds the
+    reference's numbers — no comparison is skipped because a cache is absent (rowptr, which is not a cache,
+    is compared whenever the result carries it)."""
     row, col, val = t.coo()
     assert t.sparse_sizes() == (ref.M, ref.N)
     assert np.array_equal(row.cpu().numpy(), ref.row) and np.array_equal(col.cpu().numpy(), ref.col)
     assert (val is None) == (ref.value is None)
     if val is not None:
         assert np.array_equal(val.cpu().numpy(), ref.value)
+    assert {k for k in _CACHES if getattr(t.storage, "_" + k) is not None} == set(expect_present)
     for name, want in (caches or {}).items():
         got = getattr(t.storage, "_" + name)
-        if got is not None:
-            assert np.array_equal(got.cpu().numpy(), want), name
+        if name in expect_present:
+            assert got is not None and np.array_equal(got.cpu().numpy(), want), name
+        elif got is not None:
+            assert name == "rowptr" and np.array_equal(got.cpu().numpy(), want), name
 
 
 @pytest.fixture(scope="module")
@@ -137,27 +145,36 @@ def test_slicing_vs_oracle(pair):
 
     t, st = pair
     rng = np.random.default_rng(5)
+    row_keeps, col_keeps = {"rowcount"}, {"colptr", "colcount", "csc2csr"}  # index_select builds them itself
     for sel in ([5, 0, 69, 5, 33], [], list(range(70))):
-        _same(t.index_select(0, idx(sel)), *so.index_select(st, 0, sel))
+        _same(t.index_select(0, idx(sel)), *so.index_select(st, 0, sel), expect_present=row_keeps)
     for sel in ([54, 1, 1, 20], [0], list(range(54, -1, -1))):
-        _same(t.index_select(1, idx(sel)), *so.index_select(st, 1, sel))
-    _same(t.index_select(2, idx([2, 0])), *so.index_select(st, 2, [2, 0]))
-    _same(t.index_select(-1, idx([1])), *so.index_select(st, -1, [1]))
+        _same(t.index_select(1, idx(sel)), *so.index_select(st, 1, sel), expect_present=col_keeps)
+    # a value dimension: a value-only replacement, every cache of the operand is carried — by now rowcount (asked
+    # for by the row selections), and colptr, colcount and csr2csc (by the CSC view of the column selections)
+    carried = {"rowcount", "colptr", "colcount", "csr2csc"}
+    _same(t.index_select(2, idx([2, 0])), *so.index_select(st, 2, [2, 0]), expect_present=carried)
+    _same(t.index_select(-1, idx([1])), *so.index_select(st, -1, [1]), expect_present=carried)
     pick = rng.integers(0, st.row.size, 40)
     for layout in ("coo", "csc"):
         _same(t.index_select_nnz(idx(pick), layout=layout), so.index_select_nnz(st, pick, layout))
     m0, m1, m2 = rng.random(70) < 0.4, rng.random(55) < 0.5, np.array([True, False, True])
-    _same(t.masked_select(0, torch.from_numpy(m0).cuda()), *so.masked_select(st, 0, m0))
-    _same(t.masked_select(1, torch.from_numpy(m1).cuda()), *so.masked_select(st, 1, m1))
-    _same(t.masked_select(2, torch.from_numpy(m2).cuda()), *so.masked_select(st, 2, m2))
+    _same(t.masked_select(0, torch.from_numpy(m0).cuda()), *so.masked_select(st, 0, m0), expect_present=row_keeps)
+    _same(t.masked_select(1, torch.from_numpy(m1).cuda()), *so.masked_select(st, 1, m1), expect_present=col_keeps)
+    # the csc-layout selection above asked for csc2csr: the operand now carries all five
+    _same(t.masked_select(2, torch.from_numpy(m2).cuda()), *so.masked_select(st, 2, m2), expect_present=set(_CACHES))
     keep = rng.random(st.row.size) < 0.5
     for layout in ("coo", "csc"):
         _same(t.masked_select_nnz(torch.from_numpy(keep).cuda(), layout=layout), so.masked_select_nnz(st, keep, layout))
+
+    # narrow slices what the operand carries (all five by now): rowcount (dim 0), colptr and colcount (dim 1),
+    # everything for a value dimension
+    narrow_keeps = {0: {"rowcount"}, 1: {"colptr", "colcount"}, 2: set(_CACHES), -1: set(_CACHES)}
     for dim, start, length in ((0, 10, 25), (0, -5, 5), (0, 0, 70), (1, 3, 40), (1, -10, 10), (2, 1, 2), (-1, 0, 1)):
-        _same(t.narrow(dim, start, length), *so.narrow(st, dim, start, length))
+        _same(t.narrow(dim, start, length), *so.narrow(st, dim, start, length), expect_present=narrow_keeps[dim])
     t.storage.fill_cache_()  # with every cache present the narrowed caches are the reference's slices
-    for dim, start, length in ((0, 10, 25), (1, 3, 40)):
-        _same(t.narrow(dim, start, length), *so.narrow(st, dim, start, length))
+    for dim, start, length, keeps in ((0, 10, 25, {"rowcount"}), (1, 3, 40, {"colptr", "colcount"})):
+        _same(t.narrow(dim, start, length), *so.narrow(st, dim, start, length), expect_present=keeps)
 
 
 def test_getitem_shapes_of_the_reference(kats):
