@@ -784,8 +784,11 @@ class _SegmentCsr(torch.autograd.Function):
         n = perm.numel() if perm is not None else ctx.rows
         grad = grad.contiguous()
         if ctx.mean:
-            count = (indptr[1:] - indptr[:-1]).clamp(min=1).to(grad.dtype)
-            grad = grad / count.view((-1,) + (1,) * (grad.dim() - 1))
+            # one division in fp32 (fp64 for fp64) and one rounding: a bf16 copy of the count is no
+            # longer the count from 257 on
+            wide = grad.dtype if grad.dtype == torch.float64 else torch.float32
+            count = (indptr[1:] - indptr[:-1]).clamp(min=1).to(wide)
+            grad = (grad.to(wide) / count.view((-1,) + (1,) * (grad.dim() - 1))).to(grad.dtype)
         g = _gather_rows_raw(grad, ptr2ind(indptr, n))  # the segment's gradient for each of its elements
         if perm is not None:
             acc = g if g.dtype in (torch.float32, torch.float64) else g.float()

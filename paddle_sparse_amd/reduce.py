@@ -45,13 +45,16 @@ def reduction(src: SparseTensor, dim: Optional[int] = None, reduce: str = "sum")
         if value is not None:
             st = src.storage
             if ((st.has_csr2csc() and st.has_colptr()) or st.col().numel() >= _SORT_BEATS_ATOMICS
-                    or value.dtype in _SEGMENTS_ONLY):
+                    or value.dtype in _SEGMENTS_ONLY or ops.needs_grad(value)):
                 # Same sums as the scatter of reduce.py:42, taken column by
                 # column in CSC order: no atomics (scattered device atomics
                 # run ~20 G/s on this chip), and reproducible bit for bit.
                 # value[csr2csc] is kept with the storage (st._value_in_csc_order): with it at
                 # hand the reduction is a sequential read, 0.05 ms at 20 M entries against
                 # 0.56 ms when every call gathers the values through the permutation
+                # Values that autograd tracks always come here: ops.scatter has no backward, while
+                # _value_in_csc_order and segment_csr are differentiable (and refuse min / max aloud),
+                # so a cold and a cached storage give the same gradient
                 return ops.segment_csr(st._value_in_csc_order(), st.colptr(), reduce)
             return ops.scatter(value, st.col(), src.size(1), reduce)
         if additive:

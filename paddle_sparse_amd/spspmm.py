@@ -22,6 +22,11 @@ average fewer than 32 products the sum is taken in exactly that order and fp32
 results equal a Gustavson CPU product bit for bit; longer runs are summed
 lane-strided by one wave each (a fixed order too, within fp32 rounding of the
 sequential one).
+
+The values are differentiable: when autograd tracks `valueA` or `valueB`, every
+partial product is formed from two `ops.gather_rows` (entry `owner[p]` of A, entry
+`rowptrB[colA[owner[p]]] + p - offsets[owner[p]]` of B) and the runs are added by
+`ops.segment_csr` through the sort's permutation, on the same kernels.
 """
 from __future__ import annotations
 
@@ -40,6 +45,12 @@ def _spspmm_csr(rowA, colA, valueA, rowptrB, colB, valueB, m: int, n: int):
     empty_i = torch.empty(0, dtype=torch.int64, device=device)
     has_value = valueA is not None or valueB is not None
     empty_v = torch.empty(0, dtype=dtype, device=device) if has_value else None
+    tracked = ops.needs_grad(valueA) or ops.needs_grad(valueB)
+    if tracked:
+        _check_tracked_operands(valueA, valueB, colA.numel(), colB.numel(), dtype)
+        # an empty product that is still part of the graph
+        parts = [v[:0] for v in (valueA, valueB) if v is not None]
+        empty_v = parts[0] * parts[1] if len(parts) == 2 else parts[0] * 1
     if colA.numel() == 0 or colB.numel() == 0:
         return empty_i, empty_i.clone(), empty_v
     counts = ops.spspmm_count(colA, rowptrB)
@@ -48,12 +59,18 @@ def _spspmm_csr(rowA, colA, valueA, rowptrB, colB, valueB, m: int, n: int):
     if total == 0:
         return empty_i, empty_i.clone(), empty_v
     owner = ops.ptr2ind(offsets, total)
-    keys, vals = ops.spspmm_expand(rowA, colA, valueA, rowptrB, colB, valueB, offsets, owner,
-                                   total, n, dtype)
+    if tracked:
+        # the keys come from the same kernel as on the fused route (no values: it writes keys alone), so both routes
+        # number the products alike; the values are gathered beside it, where autograd can follow
+        keys, _ = ops.spspmm_expand(rowA, colA, None, rowptrB, colB, None, offsets, owner, total, n, dtype)
+        vals = _tracked_products(colA, valueA, rowptrB, valueB, offsets, owner, total, dtype)
+    else:
+        keys, vals = ops.spspmm_expand(rowA, colA, valueA, rowptrB, colB, valueB, offsets, owner,
+                                       total, n, dtype)
     del owner, offsets, counts
     # rows of A are sorted, so keys are already grouped by C row; the sort
     # orders columns inside rows and brings equal (i, j) together
-    if vals is not None and vals.element_size() == 4:
+    if vals is not None and vals.element_size() == 4 and not tracked:
         keys, vals, scratch = ops.sort_pairs(keys, vals, m * n, keep_scratch=True)
         perm = None
     else:
@@ -69,6 +86,28 @@ def _spspmm_csr(rowA, colA, valueA, rowptrB, colB, valueB, m: int, n: int):
         elif perm is not None:
             vals = ops.gather_rows(vals, perm)
     return row, col, vals
+
+
+def _check_tracked_operands(valueA, valueB, nnzA: int, nnzB: int, dtype) -> None:
+    """spspmm_expand's checks of dtype, shape and length, for the route that reads the values through
+    ops.gather_rows instead (which takes any index on trust): made before anything is launched."""
+    for name, v, cnt in (("valueA", valueA, nnzA), ("valueB", valueB, nnzB)):
+        if v is not None and (v.dtype != dtype or v.dim() != 1 or v.numel() != cnt):
+            raise ValueError(f"{name} must be a 1-D {dtype} tensor with one entry per index")
+
+
+def _tracked_products(colA, valueA, rowptrB, valueB, offsets, owner, total: int, dtype):
+    """The partial products in the order spspmm_expand writes them, for values that autograd tracks: product p
+    pairs entry ea = owner[p] of A with entry eb = rowptrB[colA[ea]] + (p - offsets[ea]) of B, each read through
+    the differentiable ops.gather_rows.  An operand without values counts as ones.  The caller has checked the
+    operands (_check_tracked_operands); the dtypes are those spspmm_expand takes."""
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"spspmm: unsupported dtype {dtype}")
+    within = torch.arange(total, dtype=torch.int64, device=owner.device) - ops.gather_rows(offsets, owner)
+    eb = ops.gather_rows(rowptrB, ops.gather_rows(colA, owner)) + within
+    a = None if valueA is None else ops.gather_rows(valueA, owner)
+    b = None if valueB is None else ops.gather_rows(valueB, eb)
+    return a * b if a is not None and b is not None else (a if a is not None else b)
 
 
 def _spspmm_by_column(a, b):
@@ -118,13 +157,17 @@ def spspmm(indexA: torch.Tensor, valueA: Optional[torch.Tensor], indexB: torch.T
     """Matrix product of two sparse matrices given as COO (index[2, nnz], value).
     Both must be coalesced (row-major sorted, no duplicates); `coalesced=True`
     coalesces them first.  Returns the coalesced (index, value) of the [m, n]
-    product."""
+    product.  The values are differentiable in valueA and valueB."""
     if coalesced:
         indexA, valueA = coalesce(indexA, valueA, m, k)
         indexB, valueB = coalesce(indexB, valueB, k, n)
     rowA, colA = indexA[0].contiguous(), indexA[1].contiguous()
     rowB, colB = indexB[0].contiguous(), indexB[1].contiguous()
-    if _by_column_ok(valueA, valueB, m, n):
+    tracked = ops.needs_grad(valueA) or ops.needs_grad(valueB)
+    if tracked:  # before the first launch
+        dtype = valueA.dtype if valueA is not None else valueB.dtype
+        _check_tracked_operands(valueA, valueB, colA.numel(), colB.numel(), dtype)
+    if _by_column_ok(valueA, valueB, m, n) and not tracked:
         from .tensor import SparseTensor
 
         a = SparseTensor(row=rowA, col=colA, value=valueA, sparse_sizes=(m, k), is_sorted=True, trust_data=True)
@@ -143,7 +186,8 @@ def spspmm_tensor(a, b):
 
     assert a.size(1) == b.size(0), "inner dimensions differ"
     m, n = a.size(0), b.size(1)
-    if _by_column_ok(a.storage.value(), b.storage.value(), m, n):
+    value_a, value_b = a.storage.value(), b.storage.value()
+    if _by_column_ok(value_a, value_b, m, n) and not (ops.needs_grad(value_a) or ops.needs_grad(value_b)):
         row, col, value = _spspmm_by_column(a, b)
     else:
         rowA, colA, valueA = a.coo()
