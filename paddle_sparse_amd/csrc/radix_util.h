@@ -20,6 +20,8 @@ __device__ __forceinline__ unsigned digit_of(uint64_t key, int shift) {
 // memory) can interleave, and only the short counter update is serial:
 //   wave_match : (#peers below this lane) | (#peers << 8), 0xffff.. if invalid
 //   wave_rank  : rank from the packed match word + the LDS running count
+// PRECONDITION: all 64 lanes of the wave are active at the call (no divergent caller, no early
+// return above it): the ballots assume a full EXEC mask; a lane without a key passes valid = false.
 __device__ __forceinline__ uint32_t wave_match(unsigned d, bool valid) {
   // lanes whose bit b differs from mine = ballot(bit b) ^ (my bit ? ~0 : 0);
   // OR the 8 difference masks, the complement are my peers.  Written on the
