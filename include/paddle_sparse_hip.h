@@ -885,6 +885,31 @@ int psa_saint_write(const int64_t* rowptr, const int64_t* col, int64_t N, const 
                     const void* workspace, int64_t nnz_out, int64_t* rowptr_out, int64_t* row_out,
                     int64_t* col_out, int64_t* edge_out, psa_stream_t stream);
 
+/* ---- segmented softmax of stored values (the attention path: softmax over the entries of
+ * every row or column of a sparse matrix), fp32.  src, out: [n, D] row-major (D = 1 for
+ * scalar values), any 4-byte alignment; indptr int64[nseg + 1] with indptr[nseg] <= n.
+ * For every segment s and column h < D
+ *   out[j, h] = exp(src[j, h] - m[s, h]) / sum_{j' in s} exp(src[j', h] - m[s, h]),
+ * m = the segment's maximum.  perm (int64[n] or NULL): the entry at position j of the
+ * segment order is src[perm[j]] and its result goes to out[perm[j]] (softmax over the
+ * columns of a CSR matrix: indptr = colptr, perm = csr2csc, nothing is transposed).
+ * Non-finite values as torch.softmax on the dense row: a group with a NaN, a +inf or
+ * nothing but -inf is NaN throughout; -inf among finite entries gives exactly 0.  An
+ * empty segment writes nothing.
+ * Backward, from the saved output y and the upstream gradient grad (same layout and perm
+ * rule; src is not read):
+ *   grad_src[j, h] = y[j, h] * (grad[j, h] - sum_{j' in s} y[j', h] * grad[j', h]).
+ * One group of 8..64 lanes per segment; segments above 128 entries run as 128-entry
+ * chunks whose partials are folded in chunk order.  No float atomics, no host read:
+ * bitwise reproducible and capturable.  workspace: psa_segment_softmax_workspace_bytes(n, D)
+ * bytes, 16-byte aligned (0 bytes, NULL allowed, when n <= 128). */
+size_t psa_segment_softmax_workspace_bytes(int64_t n, int64_t D);
+int psa_segment_softmax(const float* src, const int64_t* perm, const int64_t* indptr, int64_t nseg, int64_t D,
+                        int64_t n, float* out, void* workspace, size_t workspace_bytes, psa_stream_t stream);
+int psa_segment_softmax_bw(const float* y, const float* grad, const int64_t* perm, const int64_t* indptr, int64_t nseg,
+                           int64_t D, int64_t n, float* grad_src, void* workspace, size_t workspace_bytes,
+                           psa_stream_t stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -1069,3 +1069,56 @@ PD_BUILD_OP(saint_subgraph)
     .Inputs({"rowptr", "col", "node_idx"})
     .Outputs({"rowptr_out", "row_out", "col_out", "edge_index"})
     .SetKernelFn(PD_KERNEL(saint_subgraph));
+
+// segment_softmax / segment_softmax_bw: softmax of the [n, D] fp32 values over every segment of ptr (per
+// column), and its backward from the saved output; with perm, position j of the segment order is row
+// perm[j].  The seam (softmax.py of the port) composes them into one PyLayer.
+namespace {
+inline void check_softmax_operands(const paddle::Tensor& a, const paddle::Tensor& ptr,
+                                   const paddle::optional<paddle::Tensor>& perm) {
+  CHECK_GPU(a);
+  CHECK_GPU(ptr);
+  CHECK_I64(ptr);
+  PD_CHECK(a.dtype() == paddle::DataType::FLOAT32, "segment_softmax takes float32 values");
+  PD_CHECK(ptr.numel() >= 1, "ptr must have at least one element");
+  PD_CHECK(a.shape().size() >= 1, "values must have at least one dim");
+  if (perm) {
+    CHECK_I64(perm.get());
+    PD_CHECK(perm.get().numel() == a.shape()[0], "perm must have one entry per value row");
+  }
+}
+}  // namespace
+
+std::vector<paddle::Tensor> segment_softmax(paddle::Tensor& src, paddle::Tensor& ptr,
+                                            const paddle::optional<paddle::Tensor>& perm) {
+  check_softmax_operands(src, ptr, perm);
+  const int64_t nseg = ptr.numel() - 1, D = row_elems(src), n = src.shape()[0];
+  auto out = paddle::empty(src.shape(), src.dtype(), src.place());
+  const size_t ws_bytes = psa_segment_softmax_workspace_bytes(n, D);
+  auto ws = scratch(ws_bytes, src.place());
+  PSA_CALL(psa_segment_softmax(f32(src), perm ? i64(perm.get()) : nullptr, i64(ptr), nseg, D, n, out.data<float>(),
+                               ws.data<uint8_t>(), ws_bytes, stream_of(src)));
+  return {out};
+}
+PD_BUILD_OP(segment_softmax)
+    .Inputs({"src", "ptr", paddle::Optional("perm")})
+    .Outputs({"out"})
+    .SetKernelFn(PD_KERNEL(segment_softmax));
+
+std::vector<paddle::Tensor> segment_softmax_bw(paddle::Tensor& y, paddle::Tensor& grad, paddle::Tensor& ptr,
+                                               const paddle::optional<paddle::Tensor>& perm) {
+  check_softmax_operands(y, ptr, perm);
+  CHECK_GPU(grad);
+  PD_CHECK(grad.dtype() == paddle::DataType::FLOAT32 && grad.shape() == y.shape(), "grad must match y");
+  const int64_t nseg = ptr.numel() - 1, D = row_elems(y), n = y.shape()[0];
+  auto out = paddle::empty(y.shape(), y.dtype(), y.place());
+  const size_t ws_bytes = psa_segment_softmax_workspace_bytes(n, D);
+  auto ws = scratch(ws_bytes, y.place());
+  PSA_CALL(psa_segment_softmax_bw(f32(y), f32(grad), perm ? i64(perm.get()) : nullptr, i64(ptr), nseg, D, n,
+                                  out.data<float>(), ws.data<uint8_t>(), ws_bytes, stream_of(y)));
+  return {out};
+}
+PD_BUILD_OP(segment_softmax_bw)
+    .Inputs({"y", "grad", "ptr", paddle::Optional("perm")})
+    .Outputs({"grad_src"})
+    .SetKernelFn(PD_KERNEL(segment_softmax_bw));

@@ -63,6 +63,8 @@ if not _running_the_builder():
         ("diag", ("remove_diag", "set_diag", "fill_diag", "get_diag")),
         ("rw", ("random_walk",)),
         ("saint", ("saint_subgraph",)),
+        ("softmax", ("softmax",)),
+        ("sddmm", ("sddmm",)),
     )
 
     __all__ = ["__version__"]

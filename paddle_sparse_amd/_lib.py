@@ -154,6 +154,11 @@ SIGNATURES = {
                                 c_void_p]),
     "psa_saint_write": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "psa_segment_softmax_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "psa_segment_softmax": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                    c_size_t, c_void_p]),
+    "psa_segment_softmax_bw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
+                                       c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

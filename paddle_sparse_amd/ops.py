@@ -1556,3 +1556,140 @@ def saint_subgraph(rowptr: torch.Tensor, col: torch.Tensor, node_idx: torch.Tens
         check(lib.psa_saint_write(_ptr(rowptr), _ptr(col), N, _ptr(node_idx), S, _ptr(ws), nnz_out,
                                   _ptr(rowptr_out), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()))
     return rowptr_out, out[0], out[1], out[2], flags
+
+
+# ---- the attention path: segmented softmax (csrc/softmax.hip) and sddmm ----------------------------
+
+def _softmax_operands(a: torch.Tensor, name: str, indptr: torch.Tensor, perm: Optional[torch.Tensor]):
+    _gpu(a, name)
+    indptr = _index(indptr, "indptr")
+    if a.dtype != torch.float32:
+        raise TypeError(f"segment_softmax: {name} must be float32 (got {a.dtype})")
+    if a.dim() < 1:
+        raise ValueError(f"{name} must have at least one dim")
+    if indptr.numel() < 1:
+        raise ValueError("indptr must have at least one element")
+    a = a.contiguous()
+    if perm is not None:
+        perm = _index(perm, "perm")
+        if perm.numel() != a.shape[0]:
+            raise ValueError("perm must have one entry per row of the values")
+    D = 1
+    for s in a.shape[1:]:
+        D *= s
+    return a, indptr, perm, indptr.numel() - 1, D
+
+
+def _segment_softmax_raw(src: torch.Tensor, indptr: torch.Tensor, perm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    src, indptr, perm, nseg, D = _softmax_operands(src, "src", indptr, perm)
+    n = src.shape[0]
+    out = torch.empty_like(src)
+    lib = _lib.load()
+    ws_bytes = lib.psa_segment_softmax_workspace_bytes(n, D)
+    ws = _workspace(ws_bytes, src.device) if ws_bytes else None
+    with _on(src.device):
+        check(lib.psa_segment_softmax(_ptr(src), _ptr(perm), _ptr(indptr), nseg, D, n, _ptr(out), _ptr(ws), ws_bytes,
+                                      _stream()))
+    return out
+
+
+def segment_softmax_bw(y: torch.Tensor, grad: torch.Tensor, indptr: torch.Tensor,
+                       perm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Backward of segment_softmax from its saved output: y * (grad - sum over the segment of y * grad),
+    per column.  Same layout and `perm` rule as the forward; fp32 only."""
+    y, indptr, perm, nseg, D = _softmax_operands(y, "y", indptr, perm)
+    _gpu(grad, "grad")
+    if grad.dtype != torch.float32:
+        raise TypeError(f"segment_softmax_bw: grad must be float32 (got {grad.dtype})")
+    if grad.shape != y.shape:
+        raise ValueError("grad must have y's shape")
+    grad = grad.contiguous()
+    n = y.shape[0]
+    out = torch.empty_like(y)
+    lib = _lib.load()
+    ws_bytes = lib.psa_segment_softmax_workspace_bytes(n, D)
+    ws = _workspace(ws_bytes, y.device) if ws_bytes else None
+    with _on(y.device):
+        check(lib.psa_segment_softmax_bw(_ptr(y), _ptr(grad), _ptr(perm), _ptr(indptr), nseg, D, n, _ptr(out), _ptr(ws),
+                                         ws_bytes, _stream()))
+    return out
+
+
+class _SegmentSoftmax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, src, indptr, perm):
+        y = _segment_softmax_raw(src, indptr, perm)
+        ctx.save_for_backward(y, indptr, perm)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        y, indptr, perm = ctx.saved_tensors
+        return segment_softmax_bw(y, grad, indptr, perm), None, None
+
+
+def segment_softmax(src: torch.Tensor, indptr: torch.Tensor, perm: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Softmax of src (fp32 [n] or [n, H]; further value dims count as columns) over every segment of
+    indptr (int64[nseg + 1]), one softmax per column.  With `perm` the entry at position j of the segment
+    order is src[perm[j]] and its result lands at out[perm[j]]: the result keeps src's order.  Entries that
+    no segment covers are left unwritten.  Differentiable in src (the backward reads the saved output)."""
+    if needs_grad(src):
+        return _SegmentSoftmax.apply(src, indptr, perm)
+    return _segment_softmax_raw(src, indptr, perm)
+
+
+def _sddmm_raw(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    rowptr, col = _index(rowptr, "rowptr"), _index(col, "col")
+    x, y = _f32(x, "x"), _f32(y, "y")
+    if rowptr.numel() < 1:
+        raise ValueError("rowptr must have at least one element")
+    M, nnz = rowptr.numel() - 1, col.numel()
+    if x.dim() != 2 or y.dim() != 2 or x.shape[0] != M or x.shape[1] != y.shape[1]:
+        raise ValueError(f"sddmm: x must be [{M}, K] and y [N, K] (got {tuple(x.shape)}, {tuple(y.shape)})")
+    K = x.shape[1]
+    if K % 4 == 0:  # the 16-byte gathers of psa_spmm_value_bw; other K (and views) take its 4-byte form
+        x, y = _aligned16(x), _aligned16(y)
+    out = torch.empty(nnz, dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    ws_bytes = lib.psa_spmm_value_bw_workspace_bytes(nnz)
+    ws = _workspace(ws_bytes, x.device) if ws_bytes else None
+    with _on(x.device):
+        check(lib.psa_spmm_value_bw(_lib.SUM, _ptr(rowptr), _ptr(col), _ptr(y), _ptr(x), M, K, nnz, _ptr(out), _ptr(ws),
+                                    ws_bytes, _stream()))
+    return out
+
+
+class _Sddmm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, rowptr, col, csc):
+        ctx.save_for_backward(x, y, rowptr, col)
+        ctx.csc = csc
+        return _sddmm_raw(rowptr, col, x, y)
+
+    @staticmethod
+    def backward(ctx, grad):
+        x, y, rowptr, col = ctx.saved_tensors
+        grad = grad.contiguous()
+        grad_x = grad_y = None
+        if ctx.needs_input_grad[0]:  # grad_x[r] = sum over the row's entries of g[e] * y[col[e]]
+            grad_x = _spmm("sum", rowptr, col, grad, y, want_arg=False)[0]
+        if ctx.needs_input_grad[1]:  # grad_y[c] = sum over the column's entries of g[e] * x[row(e)]: SpMM over the CSC view
+            csc = ctx.csc() if callable(ctx.csc) else ctx.csc
+            if csc is None:
+                N, nnz = y.shape[0], col.numel()
+                col_csc, csr2csc = index_sort(col, N, with_sorted_inputs=True, check=True)
+                csc = (ind2ptr(col_csc, N), _gather_rows_raw(ptr2ind(rowptr, nnz), csr2csc), csr2csc)
+            colptr, row_csc, csr2csc = csc
+            grad_y = _spmm("sum", colptr, row_csc, _gather_rows_raw(grad, csr2csc), x, want_arg=False)[0]
+        return grad_x, grad_y, None, None, None
+
+
+def sddmm(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, y: torch.Tensor, csc=None) -> torch.Tensor:
+    """f32[nnz]: out[e] = <x[row(e)], y[col[e]]> for every entry of the CSR pattern (rowptr, col), with x fp32
+    [M, K] and y fp32 [N, K] — psa_spmm_value_bw with mat = y, grad = x.  Differentiable in x and y:
+    grad_x = spmm_sum(rowptr, col, g, y), grad_y = the SpMM over the CSC view with g[csr2csc].  `csc`:
+    (colptr, row[csr2csc], csr2csc), or a callable returning it, when the caller has that view (a
+    SparseStorage does); without it the backward sorts `col` once."""
+    if needs_grad(x) or needs_grad(y):
+        return _Sddmm.apply(x, y, rowptr, col, csc)
+    return _sddmm_raw(rowptr, col, x, y)
