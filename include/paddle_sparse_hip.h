@@ -910,6 +910,32 @@ int psa_segment_softmax_bw(const float* y, const float* grad, const int64_t* per
                            int64_t D, int64_t n, float* grad_src, void* workspace, size_t workspace_bytes,
                            psa_stream_t stream);
 
+/* ---- multi-head attention ends: SpMM over per-head values and sddmm per head, fp32.
+ * (rowptr int64[M + 1], col int64[nnz]) is a CSR pattern with col[e] in [0, N); all dense
+ * arrays are row-major and contiguous.
+ *   psa_spmm_heads   value [nnz, H], mat [N, H, F]:
+ *                    out[r, h, f] = sum_{e in row r} value[e, h] * mat[col[e], h, f], out [M, H, F].
+ *                    out is fully written; a row without entries is 0.  A stored 0 is not
+ *                    skipped (0 * inf = NaN).
+ *   psa_sddmm_heads  x [M, H, K], y [N, H, K]: out[e, h] = <x[row(e), h, :], y[col[e], h, :]>,
+ *                    out [nnz, H].  Also the gradient of psa_spmm_heads wrt value (x = grad_out,
+ *                    y = mat, K = F); the gradients wrt the dense operands are psa_spmm_heads
+ *                    over the CSR and the CSC view.
+ * One wave per row; rows above 128 entries run as 128-entry chunks (psa_spmm_heads adds the
+ * chunks' partial rows in chunk order).  16-byte gathers when F (K) % 4 == 0 and mat and out
+ * (x and y) are 16-byte aligned, 4-byte loads otherwise: any 4-byte alignment is accepted.
+ * Every address is formed in 64-bit arithmetic (no bound on N * H * F * 4).  No float atomics,
+ * no host read: bitwise reproducible and capturable.  workspace: the matching
+ * _workspace_bytes(...) bytes, 16-byte aligned (0 bytes, NULL allowed, when nnz <= 128). */
+size_t psa_spmm_heads_workspace_bytes(int64_t nnz, int64_t H, int64_t F);
+int psa_spmm_heads(const int64_t* rowptr, const int64_t* col, const float* value, const float* mat, int64_t M,
+                   int64_t N, int64_t H, int64_t F, int64_t nnz, float* out, void* workspace,
+                   size_t workspace_bytes, psa_stream_t stream);
+size_t psa_sddmm_heads_workspace_bytes(int64_t nnz);
+int psa_sddmm_heads(const int64_t* rowptr, const int64_t* col, const float* x, const float* y, int64_t M, int64_t H,
+                    int64_t K, int64_t nnz, float* out, void* workspace, size_t workspace_bytes,
+                    psa_stream_t stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

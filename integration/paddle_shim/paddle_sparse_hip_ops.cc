@@ -1122,3 +1122,63 @@ PD_BUILD_OP(segment_softmax_bw)
     .Inputs({"y", "grad", "ptr", paddle::Optional("perm")})
     .Outputs({"grad_src"})
     .SetKernelFn(PD_KERNEL(segment_softmax_bw));
+
+// spmm_heads / sddmm_heads: the multi-head ends of the attention path.  spmm_heads(rowptr, col, value [nnz, H],
+// mat [N, H, F]) -> [M, H, F]; sddmm_heads(rowptr, col, x [M, H, K], y [N, H, K]) -> [nnz, H].  The seam composes
+// them into PyLayers as paddle_sparse_amd/ops.py::_SpmmHeads / _Sddmm do: grad_value = sddmm_heads(rowptr, col,
+// grad_out, mat); the gradients of the dense operands are spmm_heads over (rowptr, col) and over (colptr,
+// row[csr2csc]) with gather_rows(weights, csr2csc).
+namespace {
+inline void check_heads_pattern(const paddle::Tensor& rowptr, const paddle::Tensor& col) {
+  CHECK_GPU(rowptr);
+  CHECK_GPU(col);
+  CHECK_I64(rowptr);
+  CHECK_I64(col);
+  PD_CHECK(rowptr.numel() >= 1, "rowptr must have at least one element");
+}
+inline void check_heads_dense(const paddle::Tensor& a, size_t rank, const char* what) {
+  CHECK_GPU(a);
+  PD_CHECK(a.dtype() == paddle::DataType::FLOAT32, what);
+  PD_CHECK(a.shape().size() == rank, what);
+}
+}  // namespace
+
+std::vector<paddle::Tensor> spmm_heads(paddle::Tensor& rowptr, paddle::Tensor& col, paddle::Tensor& value,
+                                       paddle::Tensor& mat) {
+  check_heads_pattern(rowptr, col);
+  check_heads_dense(value, 2, "value must be float32 [nnz, H]");
+  check_heads_dense(mat, 3, "mat must be float32 [N, H, F]");
+  const int64_t M = rowptr.numel() - 1, nnz = col.numel();
+  const int64_t N = mat.shape()[0], H = mat.shape()[1], F = mat.shape()[2];
+  PD_CHECK(value.shape()[0] == nnz && value.shape()[1] == H, "value must be [nnz, H] with mat's H");
+  auto out = paddle::empty({M, H, F}, mat.dtype(), mat.place());
+  const size_t ws_bytes = psa_spmm_heads_workspace_bytes(nnz, H, F);
+  auto ws = scratch(ws_bytes, mat.place());
+  PSA_CALL(psa_spmm_heads(i64(rowptr), i64(col), f32(value), f32(mat), M, N, H, F, nnz, out.data<float>(),
+                          ws.data<uint8_t>(), ws_bytes, stream_of(mat)));
+  return {out};
+}
+PD_BUILD_OP(spmm_heads)
+    .Inputs({"rowptr", "col", "value", "mat"})
+    .Outputs({"out"})
+    .SetKernelFn(PD_KERNEL(spmm_heads));
+
+std::vector<paddle::Tensor> sddmm_heads(paddle::Tensor& rowptr, paddle::Tensor& col, paddle::Tensor& x,
+                                        paddle::Tensor& y) {
+  check_heads_pattern(rowptr, col);
+  check_heads_dense(x, 3, "x must be float32 [M, H, K]");
+  check_heads_dense(y, 3, "y must be float32 [N, H, K]");
+  const int64_t M = rowptr.numel() - 1, nnz = col.numel();
+  const int64_t H = x.shape()[1], K = x.shape()[2];
+  PD_CHECK(x.shape()[0] == M && y.shape()[1] == H && y.shape()[2] == K, "x must be [M, H, K] and y [N, H, K]");
+  auto out = paddle::empty({nnz, H}, x.dtype(), x.place());
+  const size_t ws_bytes = psa_sddmm_heads_workspace_bytes(nnz);
+  auto ws = scratch(ws_bytes, x.place());
+  PSA_CALL(psa_sddmm_heads(i64(rowptr), i64(col), f32(x), f32(y), M, H, K, nnz, out.data<float>(), ws.data<uint8_t>(),
+                           ws_bytes, stream_of(x)));
+  return {out};
+}
+PD_BUILD_OP(sddmm_heads)
+    .Inputs({"rowptr", "col", "x", "y"})
+    .Outputs({"out"})
+    .SetKernelFn(PD_KERNEL(sddmm_heads));

@@ -159,6 +159,12 @@ SIGNATURES = {
                                     c_size_t, c_void_p]),
     "psa_segment_softmax_bw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
                                        c_void_p, c_size_t, c_void_p]),
+    "psa_spmm_heads_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "psa_spmm_heads": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64,
+                               c_void_p, c_void_p, c_size_t, c_void_p]),
+    "psa_sddmm_heads_workspace_bytes": (c_size_t, [c_int64]),
+    "psa_sddmm_heads": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p,
+                                c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

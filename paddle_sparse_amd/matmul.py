@@ -350,11 +350,15 @@ class _SpMM(torch.autograd.Function):
 
 
 def spmm_sparse(src: SparseTensor, other: torch.Tensor, reduce: str = "sum") -> torch.Tensor:
-    """out = reduce-SpMM(src, other) for a dense `other` [N, K] (fp32)."""
+    """out = reduce-SpMM(src, other) for a dense `other` [N, K] (fp32), or [N, H, F]: with values
+    [nnz, H] one weight per head (reduce sum only, out [M, H, F]), with scalar or no values the 2-D
+    product on other.reshape(N, H * F)."""
     if reduce == "add":
         reduce = "sum"
     if reduce not in ("sum", "mean", "min", "max"):
         raise ValueError(reduce)
+    if other.dim() == 3 and other.shape[0] == src.sparse_size(1):
+        return _spmm_3d(src, other, reduce)
     if other.dim() != 2 or other.shape[0] != src.sparse_size(1):
         raise ValueError(f"dense operand must be [{src.sparse_size(1)}, K]")
     value = src.storage.value()
@@ -363,6 +367,28 @@ def spmm_sparse(src: SparseTensor, other: torch.Tensor, reduce: str = "sum") -> 
     # forward() runs with grad mode off and sees requires_grad flags only: whether a
     # backward can follow at all is decided here
     return _SpMM.apply(value, other, src.storage, reduce, torch.is_grad_enabled())
+
+
+def _spmm_3d(src: SparseTensor, other: torch.Tensor, reduce: str) -> torch.Tensor:
+    """`other` [N, H, F].  Values [nnz, H]: psa_spmm_heads (csrc/spmm_heads.hip), sum only.  Scalar or no
+    values weigh every head alike: the 2-D product on the [N, H * F] view, reshaped back."""
+    st = src.storage
+    value = st.value()
+    N, H, F = other.shape
+    if value is None or value.dim() == 1:
+        return spmm_sparse(src, other.reshape(N, H * F), reduce).reshape(src.sparse_size(0), H, F)
+    if value.dim() != 2 or value.shape[1] != H:
+        raise ValueError(f"spmm with a [{N}, {H}, {F}] operand needs values [nnz] or [nnz, {H}] (got {tuple(value.shape)})")
+    if value.dtype != torch.float32 or other.dtype != torch.float32:
+        raise TypeError(f"spmm over per-head values is float32 only (got {value.dtype}, {other.dtype})")
+    if reduce != "sum":
+        raise NotImplementedError(f"spmm over per-head values supports reduce='sum' only (got {reduce!r})")
+
+    def csc():  # asked for by the backward of `other` only
+        csr2csc = st.csr2csc()
+        return st.colptr(), st._row_in_csc_order(), csr2csc
+
+    return ops.spmm_heads(st.rowptr(), st.col(), value, other, csc=csc)
 
 
 def matmul(src: SparseTensor, other, reduce: str = "sum") -> torch.Tensor:

@@ -1664,6 +1664,8 @@ class _Sddmm(torch.autograd.Function):
     def forward(ctx, x, y, rowptr, col, csc):
         ctx.save_for_backward(x, y, rowptr, col)
         ctx.csc = csc
+        if _is_heads(x, y):
+            return _sddmm_heads_raw(rowptr, col, x, y)
         return _sddmm_raw(rowptr, col, x, y)
 
     @staticmethod
@@ -1671,17 +1673,23 @@ class _Sddmm(torch.autograd.Function):
         x, y, rowptr, col = ctx.saved_tensors
         grad = grad.contiguous()
         grad_x = grad_y = None
+        if x.dim() == 3:  # per head: both gradients are psa_spmm_heads with the [nnz, H] gradient as the values
+            if ctx.needs_input_grad[0]:
+                grad_x = _spmm_heads_raw(rowptr, col, grad, y)
+            if ctx.needs_input_grad[1]:
+                grad_y = _spmm_heads_transposed(_csc_view(ctx.csc, rowptr, col, y.shape[0]), grad, x)
+            return grad_x, grad_y, None, None, None
         if ctx.needs_input_grad[0]:  # grad_x[r] = sum over the row's entries of g[e] * y[col[e]]
             grad_x = _spmm("sum", rowptr, col, grad, y, want_arg=False)[0]
         if ctx.needs_input_grad[1]:  # grad_y[c] = sum over the column's entries of g[e] * x[row(e)]: SpMM over the CSC view
-            csc = ctx.csc() if callable(ctx.csc) else ctx.csc
-            if csc is None:
-                N, nnz = y.shape[0], col.numel()
-                col_csc, csr2csc = index_sort(col, N, with_sorted_inputs=True, check=True)
-                csc = (ind2ptr(col_csc, N), _gather_rows_raw(ptr2ind(rowptr, nnz), csr2csc), csr2csc)
-            colptr, row_csc, csr2csc = csc
+            colptr, row_csc, csr2csc = _csc_view(ctx.csc, rowptr, col, y.shape[0])
             grad_y = _spmm("sum", colptr, row_csc, _gather_rows_raw(grad, csr2csc), x, want_arg=False)[0]
         return grad_x, grad_y, None, None, None
+
+
+def _is_heads(x, y) -> bool:
+    """Both operands 3-D: the per-head form.  Everything else goes to the 2-D call and its errors."""
+    return isinstance(x, torch.Tensor) and isinstance(y, torch.Tensor) and x.dim() == 3 and y.dim() == 3
 
 
 def sddmm(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, y: torch.Tensor, csc=None) -> torch.Tensor:
@@ -1689,7 +1697,103 @@ def sddmm(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, y: torch.Ten
     [M, K] and y fp32 [N, K] — psa_spmm_value_bw with mat = y, grad = x.  Differentiable in x and y:
     grad_x = spmm_sum(rowptr, col, g, y), grad_y = the SpMM over the CSC view with g[csr2csc].  `csc`:
     (colptr, row[csr2csc], csr2csc), or a callable returning it, when the caller has that view (a
-    SparseStorage does); without it the backward sorts `col` once."""
+    SparseStorage does); without it the backward sorts `col` once.
+    Per head: x fp32 [M, H, K] and y fp32 [N, H, K] give f32[nnz, H], out[e, h] = <x[row(e), h], y[col[e], h]>
+    (psa_sddmm_heads), with both gradients from psa_spmm_heads."""
     if needs_grad(x) or needs_grad(y):
         return _Sddmm.apply(x, y, rowptr, col, csc)
+    if _is_heads(x, y):
+        return _sddmm_heads_raw(rowptr, col, x, y)
     return _sddmm_raw(rowptr, col, x, y)
+
+
+# ---- multi-head ends of the attention path (csrc/spmm_heads.hip) ----------------------------------
+
+def _heads_pattern(rowptr: torch.Tensor, col: torch.Tensor):
+    rowptr, col = _index(rowptr, "rowptr"), _index(col, "col")
+    if rowptr.numel() < 1:
+        raise ValueError("rowptr must have at least one element")
+    return rowptr, col, rowptr.numel() - 1, col.numel()
+
+
+def _spmm_heads_raw(rowptr: torch.Tensor, col: torch.Tensor, value: torch.Tensor, mat: torch.Tensor) -> torch.Tensor:
+    rowptr, col, M, nnz = _heads_pattern(rowptr, col)
+    value, mat = _f32(value, "value"), _f32(mat, "mat")
+    if mat.dim() != 3:
+        raise ValueError(f"spmm over per-head values: the dense operand must be [N, H, F] (got {tuple(mat.shape)})")
+    N, H, F = mat.shape
+    if value.dim() != 2 or value.shape[0] != nnz or value.shape[1] != H:
+        raise ValueError(f"spmm over per-head values: value must be [{nnz}, {H}] (got {tuple(value.shape)})")
+    if F % 4 == 0:  # the 16-byte gathers; other F (and views) take the 4-byte form
+        mat = _aligned16(mat)
+    out = torch.empty((M, H, F), dtype=torch.float32, device=mat.device)
+    lib = _lib.load()
+    ws_bytes = lib.psa_spmm_heads_workspace_bytes(nnz, H, F)
+    ws = _workspace(ws_bytes, mat.device) if ws_bytes else None
+    with _on(mat.device):
+        check(lib.psa_spmm_heads(_ptr(rowptr), _ptr(col), _ptr(value), _ptr(mat), M, N, H, F, nnz, _ptr(out), _ptr(ws),
+                                 ws_bytes, _stream()))
+    return out
+
+
+def _sddmm_heads_raw(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    rowptr, col, M, nnz = _heads_pattern(rowptr, col)
+    x, y = _f32(x, "x"), _f32(y, "y")
+    if x.dim() != 3 or y.dim() != 3 or x.shape[0] != M or x.shape[1:] != y.shape[1:]:
+        raise ValueError(f"sddmm: x must be [{M}, H, K] and y [N, H, K] (got {tuple(x.shape)}, {tuple(y.shape)})")
+    H, K = x.shape[1], x.shape[2]
+    if K % 4 == 0:
+        x, y = _aligned16(x), _aligned16(y)
+    out = torch.empty((nnz, H), dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    ws_bytes = lib.psa_sddmm_heads_workspace_bytes(nnz)
+    ws = _workspace(ws_bytes, x.device) if ws_bytes else None
+    with _on(x.device):
+        check(lib.psa_sddmm_heads(_ptr(rowptr), _ptr(col), _ptr(x), _ptr(y), M, H, K, nnz, _ptr(out), _ptr(ws), ws_bytes,
+                                  _stream()))
+    return out
+
+
+def _csc_view(csc, rowptr: torch.Tensor, col: torch.Tensor, N: int):
+    """(colptr, row[csr2csc], csr2csc): the caller's (a tuple or a callable returning one), else built by one sort of col."""
+    csc = csc() if callable(csc) else csc
+    if csc is None:
+        col_csc, csr2csc = index_sort(col, N, with_sorted_inputs=True, check=True)
+        csc = (ind2ptr(col_csc, N), _gather_rows_raw(ptr2ind(rowptr, col.numel()), csr2csc), csr2csc)
+    return csc
+
+
+def _spmm_heads_transposed(csc, weight: torch.Tensor, dense: torch.Tensor) -> torch.Tensor:
+    """out[c, h, :] = sum over the column's entries of weight[e, h] * dense[row(e), h, :]: psa_spmm_heads over
+    the CSC view, the [nnz, H] weights brought to CSC order by a row gather."""
+    colptr, row_csc, csr2csc = csc
+    return _spmm_heads_raw(colptr, row_csc, _gather_rows_raw(weight, csr2csc), dense)
+
+
+class _SpmmHeads(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, value, mat, rowptr, col, csc):
+        ctx.save_for_backward(value, mat, rowptr, col)
+        ctx.csc = csc
+        return _spmm_heads_raw(rowptr, col, value, mat)
+
+    @staticmethod
+    def backward(ctx, grad):
+        value, mat, rowptr, col = ctx.saved_tensors
+        grad = grad.contiguous()
+        grad_value = grad_mat = None
+        if ctx.needs_input_grad[0]:  # grad_value[e, h] = <grad[row(e), h, :], mat[col[e], h, :]>
+            grad_value = _sddmm_heads_raw(rowptr, col, grad, mat)
+        if ctx.needs_input_grad[1]:  # grad_mat[c] = sum over the column's entries of value[e] * grad[row(e)]
+            grad_mat = _spmm_heads_transposed(_csc_view(ctx.csc, rowptr, col, mat.shape[0]), value, grad)
+        return grad_value, grad_mat, None, None, None
+
+
+def spmm_heads(rowptr: torch.Tensor, col: torch.Tensor, value: torch.Tensor, mat: torch.Tensor, csc=None) -> torch.Tensor:
+    """f32[M, H, F]: out[r, h, :] = sum over the entries of row r of value[e, h] * mat[col[e], h, :], with value
+    fp32 [nnz, H] and mat fp32 [N, H, F] — the aggregation of a multi-head attention layer in one launch.
+    Differentiable in value (psa_sddmm_heads of the upstream gradient and mat) and in mat (the same
+    product over the CSC view).  `csc` as for sddmm."""
+    if needs_grad(value) or needs_grad(mat):
+        return _SpmmHeads.apply(value, mat, rowptr, col, csc)
+    return _spmm_heads_raw(rowptr, col, value, mat)

@@ -14,8 +14,17 @@ DESIGN.md section 3.8 (forward nnz*4D read + nnz*4D written + (M+1)*8; backward 
 written) as achieved bytes/s and as a fraction of 8 TB/s.  Results are compared where the restatement
 is deterministic enough to (max relative difference printed; the torch side adds with atomics).
 
-usage: python tools/attention_bench.py [--quick] [--once]
-  --quick  config 3 only;  --once  one call of each of our ops and nothing else (for a kernel trace)"""
+The multi-head lines (H = 8, K = F = 16 and 64: sddmm, the SpMM over per-head values forward and forward +
+backward, the whole step) run the one-launch form beside (a) the per-head Python loop over the 2-D ops, slice
+copies and the final stack included, and (b) the restatement in torch ops, the three alternating call by call;
+each timing is the median with its [min .. max] over the rounds, the spread a difference has to exceed.  Byte
+model of DESIGN.md section 3.9: the SpMM reads nnz*(8 + 4H + 4HF) and writes M*4HF, sddmm reads the same and
+writes nnz*4H.  A side whose operands or temporaries would not fit the device's free memory is reported as not
+run instead of being tried.
+
+usage: python tools/attention_bench.py [--quick] [--once] [--heads]
+  --quick  config 3 only;  --once  one call of each of our ops and nothing else (for a kernel trace);
+  --heads  the multi-head lines only"""
 import statistics
 import sys
 from pathlib import Path
@@ -64,6 +73,117 @@ def line(label, t_ours, t_theirs, model_bytes=None):
           flush=True)
 
 
+def alternate_all(fns):
+    """(median, min, max) ms of each callable, all alternating call by call after 3 warm-up calls of each."""
+    for _ in range(3):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    times = [[] for _ in fns]
+    for _ in range(ROUNDS):
+        for fn, t in zip(fns, times):
+            t.append(one_ms(fn))
+    return [(statistics.median(t), min(t), max(t)) for t in times]
+
+
+def fits(nbytes) -> bool:
+    torch.cuda.empty_cache()
+    return nbytes < 0.8 * torch.cuda.mem_get_info(dev)[0]
+
+
+def heads_line(label, sides, model_bytes=None):
+    """sides: [(name, callable or None)], ours first; a None side is printed as not run."""
+    live = [(n, f) for n, f in sides if f is not None]
+    res = dict(zip((n for n, _ in live), alternate_all([f for _, f in live])))
+    ours = res[sides[0][0]][0]
+    parts = []
+    for name, fn in sides:
+        if fn is None:
+            parts.append(f"{name} not run (memory)")
+            continue
+        med, lo, hi = res[name]
+        ratio = "" if name == sides[0][0] else f" x{med / ours:5.2f}" + (" SLOWER" if med < ours else "")
+        parts.append(f"{name} {med:9.3f} ms [{lo:.3f} .. {hi:.3f}]{ratio}")
+    tail = ""
+    if model_bytes is not None:
+        rate = model_bytes / (ours * 1e-3)
+        tail = f"   model {model_bytes / 1e9:6.3f} GB  {rate / 1e12:5.2f} TB/s = {rate / PEAK:4.2f} of 8 TB/s"
+    print(f"   {label:34s} " + "   ".join(parts) + tail, flush=True)
+
+
+def run_heads(N, rowptr, col, row, gen, once):
+    nnz, H = col.numel(), 8
+    A = SparseTensor(rowptr=rowptr, col=col, sparse_sizes=(N, N), is_sorted=True, trust_data=True)
+    A.storage.csr2csc()  # the CSC view of the backward, built once as a training loop has it
+    for K in (16, 64):
+        F = K
+        dense, edge, wide = N * H * K * 4, nnz * H * 4, nnz * H * K * 4
+        if not fits(10 * dense + 8 * edge):  # q, k, v, the upstream gradient, three gradients, results of two sides
+            print(f"   H = {H}, K = F = {K}: not run, the operands and gradients alone take {10 * dense / 1e9:.0f} GB", flush=True)
+            continue
+        q = torch.randn((N, H, K), generator=gen, device=dev) * 0.125
+        k = torch.randn((N, H, K), generator=gen, device=dev)
+        v = torch.randn((N, H, F), generator=gen, device=dev)
+        go = torch.randn((N, H, F), generator=gen, device=dev)
+        att = psa.sddmm(A, q, k).softmax(dim=1).storage.value()
+        Aw = A.set_value(att, layout="coo")
+
+        def per_head(h, qq=q, kk=k):  # one head's scores through the 2-D op (the slices are copied inside it)
+            return psa.sddmm(A, qq[:, h], kk[:, h])
+
+        def sddmm_loop():
+            return torch.stack([per_head(h).storage.value() for h in range(H)], dim=1)
+
+        def spmm_loop(w=att, vv=v):
+            return torch.stack([A.set_value(w[:, h].contiguous(), layout="coo") @ vv[:, h] for h in range(H)], dim=1)
+
+        def spmm_torch(w=att, vv=v):
+            return torch.zeros((N, H, F), device=dev).index_add_(0, row, w[:, :, None] * vv[col])
+
+        def with_grad(fn):
+            def run():
+                w, vv = att.detach().requires_grad_(), v.detach().requires_grad_()
+                fn(w, vv).backward(go)
+            return run
+
+        def step(kind):
+            def run():
+                qq, kk, vv = (t.detach().requires_grad_() for t in (q, k, v))
+                if kind == "ours":
+                    out = psa.sddmm(A, qq, kk).softmax(dim=1) @ vv
+                elif kind == "loop":
+                    out = torch.stack([per_head(h, qq, kk).softmax(dim=1) @ vv[:, h] for h in range(H)], dim=1)
+                else:
+                    a = torch_softmax((qq[row] * kk[col]).sum(-1), row, N)
+                    out = torch.zeros((N, H, F), device=dev).index_add_(0, row, a[:, :, None] * vv[col])
+                out.backward(go)
+            return run
+
+        step("ours")()
+        if once:
+            continue
+        print(f"   H = {H}, K = F = {K}: max |one launch - per-head loop| = "
+              f"{float((psa.sddmm(A, q, k).storage.value() - sddmm_loop()).abs().max()):.2e} (sddmm), "
+              f"{float(((Aw @ v) - spmm_loop()).abs().max()):.2e} (SpMM)", flush=True)
+        spmm_bytes = nnz * (8 + 4 * H + 4 * H * F) + N * 4 * H * F
+        heads_line(f"sddmm, H = {H}, K = {K}",
+                   [("one launch", lambda: psa.sddmm(A, q, k)), ("per-head loop", sddmm_loop),
+                    ("torch ops", (lambda: (q[row] * k[col]).sum(-1)) if fits(3 * wide) else None)],
+                   nnz * (8 + 4 * H + 4 * H * K) + nnz * 4 * H)
+        heads_line(f"SpMM heads forward, F = {F}",
+                   [("one launch", lambda: Aw @ v), ("per-head loop", spmm_loop),
+                    ("torch ops", spmm_torch if fits(3 * wide) else None)], spmm_bytes)
+        heads_line(f"SpMM heads fwd + bwd, F = {F}",
+                   [("one launch", with_grad(lambda w, vv: A.set_value(w, layout="coo") @ vv)),
+                    ("per-head loop", with_grad(spmm_loop)),
+                    ("torch ops", with_grad(spmm_torch) if fits(6 * wide) else None)])
+        heads_line(f"attention step fwd + bwd, K = F = {K}",
+                   [("one launch", step("ours")), ("per-head loop", step("loop")),
+                    ("torch ops", step("torch") if fits(12 * wide) else None)])
+        del q, k, v, go, att, Aw
+        torch.cuda.empty_cache()
+
+
 def torch_softmax(v, row, M):
     shape = (M,) + tuple(v.shape[1:])
     m = torch.zeros(shape, device=dev).scatter_reduce(0, row.view((-1,) + (1,) * (v.dim() - 1)).expand_as(v), v, "amax",
@@ -98,7 +218,7 @@ def rmat24():
     return N, rowptr, col
 
 
-def run(name, make, once):
+def run(name, make, once, heads_only=False):
     N, rowptr, col = make()
     nnz = col.numel()
     row = ops.ptr2ind(rowptr, nnz)
@@ -106,6 +226,9 @@ def run(name, make, once):
     print(f"== {name}: {N} x {N}, {nnz} entries, longest row {int(deg.max())}, "
           f"{int((deg > 128).sum())} rows above 128 entries", flush=True)
     gen = torch.Generator(device=dev).manual_seed(9)
+    if heads_only:
+        run_heads(N, rowptr, col, row, gen, once)
+        return
     for D in (1, 8):
         shape = (nnz,) if D == 1 else (nnz, D)
         v = torch.randn(shape, generator=gen, device=dev)
@@ -156,7 +279,10 @@ def run(name, make, once):
         line(f"sddmm forward, K = {K}", t_o, t_t)
         t_o, t_t = alternate(step_ours, step_torch)
         line(f"attention step fwd + bwd, K = {K}", t_o, t_t)
-    del A, q, k, val, go, s, rowptr, col, row
+    del A, q, k, val, go, s
+    torch.cuda.empty_cache()
+    run_heads(N, rowptr, col, row, gen, once)
+    del rowptr, col, row
     torch.cuda.empty_cache()
 
 
@@ -164,6 +290,7 @@ if __name__ == "__main__":
     torch.cuda.set_device(dev)
     print(f"device: {torch.cuda.get_device_name(dev)}", flush=True)
     once = "--once" in sys.argv
-    run("config-3 shape", config3, once)
+    heads_only = "--heads" in sys.argv
+    run("config-3 shape", config3, once, heads_only)
     if "--quick" not in sys.argv:
-        run("R-MAT 24", rmat24, once)
+        run("R-MAT 24", rmat24, once, heads_only)
