@@ -936,6 +936,44 @@ int psa_sddmm_heads(const int64_t* rowptr, const int64_t* col, const float* x, c
                     int64_t K, int64_t nnz, float* out, void* workspace, size_t workspace_bytes,
                     psa_stream_t stream);
 
+/* ---- fused sparse attention: sddmm + row softmax + SpMM in one pass per row, fp32.  Pattern and
+ * layouts as above: q [M, H, K], k [N, H, K], v [N, H, F]; bias NULL, or [nnz] (bias_heads = 1,
+ * shared by the heads) or [nnz, H] (bias_heads = H); H, K, F >= 1.
+ *   s[e, h]      = scale * <q[row(e), h, :], k[col[e], h, :]> (+ bias)
+ *   p[e, h]      = exp(s[e, h] - m[r, h]) / l[r, h],  m = the row's maximum of s[., h],
+ *                  l = sum over the row of exp(s - m)
+ *   out[r, h, :] = sum_{e in row r} p[e, h] * v[col[e], h, :]
+ *   psa_attention_fw          writes out [M, H, F] and stat [M, H, 2] = {m, l} (the pair, not m + log l),
+ *                             both fully; nothing per entry is written.  A row without entries gives
+ *                             out = 0 and stat = {-inf, 0}.
+ *   psa_attention_bw_entries  the per-entry half of the backward: with delta[r, h] =
+ *                             <grad_out[r, h, :], out[r, h, :]> and dP[e, h] = <grad_out[row(e), h, :],
+ *                             v[col[e], h, :]> it recomputes s and writes p [nnz, H] and
+ *                             ds [nnz, H] = p * (dP - delta); a row without entries writes nothing.
+ *                             The gradients are psa_spmm_heads calls: grad_q = scale * (ds, k) over
+ *                             the CSR view, grad_k = scale * (ds, q) and grad_v = (p, grad_out) over the
+ *                             CSC view, grad_bias = ds (summed over the heads for bias_heads = 1).
+ * Non-finite values as psa_segment_softmax and psa_spmm_heads: a row and head whose scores hold a NaN,
+ * a +inf or nothing but -inf is NaN in out[r, h, :]; -inf among finite scores has weight exactly 0; no
+ * zero skipping (0 * inf = NaN).
+ * One wave per row with a running {m, l} per head (online softmax); rows above 128 entries run as
+ * 128-entry chunks whose {m, l, partial row} are merged in chunk order.  16-byte gathers when
+ * K % 4 == 0, F % 4 == 0 and q, k, v, out (and grad_out) are 16-byte aligned, 4-byte loads otherwise:
+ * any 4-byte alignment is accepted.  Every address is formed in 64-bit arithmetic.  exp is expf.  No
+ * float atomics, no host read: bitwise reproducible and capturable.  workspace, 16-byte aligned (0
+ * bytes, NULL allowed, when nnz <= 128): psa_attention_workspace_bytes(nnz, H, F) bytes for the
+ * forward; the backward needs no more than the same call gives. */
+size_t psa_attention_workspace_bytes(int64_t nnz, int64_t H, int64_t F);
+int psa_attention_fw(const int64_t* rowptr, const int64_t* col, const float* q, const float* k, const float* v,
+                     const float* bias, int64_t bias_heads, float scale, int64_t M, int64_t N, int64_t H, int64_t K,
+                     int64_t F, int64_t nnz, float* out, float* stat, void* workspace, size_t workspace_bytes,
+                     psa_stream_t stream);
+int psa_attention_bw_entries(const int64_t* rowptr, const int64_t* col, const float* q, const float* k, const float* v,
+                             const float* bias, int64_t bias_heads, float scale, const float* grad_out,
+                             const float* out, const float* stat, int64_t M, int64_t N, int64_t H, int64_t K, int64_t F,
+                             int64_t nnz, float* p, float* ds, void* workspace, size_t workspace_bytes,
+                             psa_stream_t stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -65,6 +65,7 @@ if not _running_the_builder():
         ("saint", ("saint_subgraph",)),
         ("softmax", ("softmax",)),
         ("sddmm", ("sddmm",)),
+        ("attention", ("attention",)),
     )
 
     __all__ = ["__version__"]

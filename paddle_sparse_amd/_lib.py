@@ -6,7 +6,7 @@ ops fails loudly — there is no CPU or eager fallback anywhere in this package.
 from __future__ import annotations
 
 import ctypes
-from ctypes import c_int, c_int64, c_size_t, c_uint64, c_void_p, c_char_p
+from ctypes import c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p, c_char_p
 from pathlib import Path
 
 # The framework must bring its HIP runtime into the process FIRST: the core
@@ -165,6 +165,13 @@ SIGNATURES = {
     "psa_sddmm_heads_workspace_bytes": (c_size_t, [c_int64]),
     "psa_sddmm_heads": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p,
                                 c_void_p, c_size_t, c_void_p]),
+    "psa_attention_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "psa_attention_fw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_int64,
+                                 c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
+                                 c_void_p]),
+    "psa_attention_bw_entries": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float,
+                                         c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                         c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

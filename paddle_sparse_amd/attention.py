@@ -1,0 +1,68 @@
+"""attention — sddmm, the row softmax and the aggregation of an attention layer (GAT, graph
+transformers) as one op:
+
+    s[e, h]      = scale * <q[row(e), h], k[col(e), h]>  (+ the stored value of e with bias=True)
+    p[., h]      = softmax of s[., h] over the entries of each row
+    out[r, h, :] = sum over the entries of row r of p[e, h] * v[col(e), h, :]
+
+It computes what `sddmm(A, q, k).softmax(dim=1) @ v` computes, in one pass per row with a running
+maximum and sum (csrc/attention.hip: psa_attention_fw), and writes nothing per entry: autograd
+keeps q, k, v, the output and {max, sum} per row and head, where the chain keeps two [nnz, H]
+tensors.  The backward recomputes the scores (psa_attention_bw_entries) and takes the gradients
+from psa_spmm_heads over the CSR and the CSC view.  The chain of the three ops stays as it is.
+
+Non-finite values: a row and head whose scores hold a NaN, a +inf or nothing but -inf is NaN in
+out[r, h, :]; a -inf score among finite ones has weight exactly 0 (a mask); weight 0 against an
+inf in v is NaN (no zero skipping); a row without entries gives 0.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import ops
+from .tensor import SparseTensor
+
+
+def attention(src: SparseTensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float = 1.0,
+              bias: bool = False) -> torch.Tensor:
+    """Dense fp32 [M, H, F] from q fp32 [M, H, K], k fp32 [N, H, K] and v fp32 [N, H, F] over the pattern of
+    `src`; 2-D q [M, K], k [N, K], v [N, F] are one head and give [M, F].  With bias=False the stored values
+    of `src` are NOT read; with bias=True they must be fp32 [nnz] (shared by the heads) or [nnz, H] and are
+    added to the scaled scores (-inf masks an entry).  Differentiable in q, k, v and, when they are tracked,
+    the values; `scale` is a Python float."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"attention: {name} must be a torch.Tensor")
+        if t.dtype != torch.float32:
+            raise TypeError(f"attention: {name} must be float32 (got {t.dtype})")
+        if t.dim() not in (2, 3):
+            raise ValueError(f"attention: {name} must be 2-D, or 3-D [rows, H, width]")
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)):
+        raise TypeError("attention: scale must be a float")
+    if not isinstance(bias, bool):
+        raise TypeError("attention: bias must be a bool (the bias itself is the stored values of src)")
+    M, N = src.sparse_size(0), src.sparse_size(1)
+    if not (q.dim() == k.dim() == v.dim()) or q.shape[0] != M or k.shape[0] != N or v.shape[0] != N \
+            or q.shape[1:] != k.shape[1:] or (q.dim() == 3 and v.shape[1] != q.shape[1]):
+        raise ValueError(f"attention: q, k, v must be [{M}, K], [{N}, K], [{N}, F] or [{M}, H, K], [{N}, H, K], "
+                         f"[{N}, H, F] (got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)})")
+    st = src.storage
+    value = None
+    if bias:
+        value = st.value()
+        nnz, H = st.col().numel(), (q.shape[1] if q.dim() == 3 else 1)
+        if value is None:
+            raise ValueError("attention: bias=True needs stored values")
+        if value.dtype != torch.float32:
+            raise TypeError(f"attention: bias=True takes float32 values (got {value.dtype})")
+        if value.shape not in ((nnz,), (nnz, H)):
+            raise ValueError(f"attention: bias=True takes values [{nnz}] or [{nnz}, {H}] (got {tuple(value.shape)})")
+
+    def csc():  # asked for by the backward of k and v only
+        csr2csc = st.csr2csc()
+        return st.colptr(), st._row_in_csc_order(), csr2csc
+
+    return ops.attention(st.rowptr(), st.col(), q, k, v, bias=value, scale=float(scale), csc=csc)
+
+
+SparseTensor.attention = lambda self, q, k, v, scale=1.0, bias=False: attention(self, q, k, v, scale, bias)

@@ -1797,3 +1797,140 @@ def spmm_heads(rowptr: torch.Tensor, col: torch.Tensor, value: torch.Tensor, mat
     if needs_grad(value) or needs_grad(mat):
         return _SpmmHeads.apply(value, mat, rowptr, col, csc)
     return _spmm_heads_raw(rowptr, col, value, mat)
+
+
+# ---- fused attention: sddmm + row softmax + SpMM in one pass (csrc/attention.hip) -------------------
+
+def _attention_operands(rowptr, col, q, k, v, bias):
+    """The checked, contiguous operands in heads form, plus (M, N, H, K, F, nnz) and whether the caller gave the
+    2-D form."""
+    rowptr, col, M, nnz = _heads_pattern(rowptr, col)
+    q, k, v = _f32(q, "q"), _f32(k, "k"), _f32(v, "v")
+    dims = {q.dim(), k.dim(), v.dim()}
+    if dims not in ({2}, {3}):
+        raise ValueError(f"attention: q, k, v must all be 2-D, or all 3-D [rows, H, width] "
+                         f"(got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)})")
+    flat = q.dim() == 2
+    if flat:
+        q, k, v = q.unsqueeze(1), k.unsqueeze(1), v.unsqueeze(1)
+    H, K = q.shape[1], q.shape[2]
+    N, F = k.shape[0], v.shape[2]
+    if q.shape[0] != M or k.shape[1:] != q.shape[1:] or v.shape[0] != N or v.shape[1] != H:
+        raise ValueError(f"attention: q must be [{M}, H, K], k [N, H, K] and v [N, H, F] "
+                         f"(got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)})")
+    if H < 1 or K < 1 or F < 1:
+        raise ValueError("attention: H, K and F must be at least 1")
+    if bias is not None:
+        bias = _f32(bias, "bias")
+        if bias.shape not in ((nnz,), (nnz, H)):
+            raise ValueError(f"attention: bias must be [{nnz}] or [{nnz}, {H}] (got {tuple(bias.shape)})")
+    if K % 4 == 0 and F % 4 == 0:  # the 16-byte form; other widths (and views) take the 4-byte form
+        q, k, v = _aligned16(q), _aligned16(k), _aligned16(v)
+    return rowptr, col, q, k, v, bias, (M, N, H, K, F, nnz), flat
+
+
+def _bias_heads(bias: Optional[torch.Tensor]) -> int:
+    return 1 if bias is None or bias.dim() == 1 else bias.shape[1]
+
+
+def _attention_fw_raw(rowptr, col, q, k, v, bias, scale: float):
+    """(out [M, H, F], stat [M, H, 2] = {row maximum, sum of exp(s - maximum)}) from checked heads-form operands."""
+    M, H, K = q.shape
+    N, F, nnz = k.shape[0], v.shape[2], col.numel()
+    out = torch.empty((M, H, F), dtype=torch.float32, device=q.device)
+    stat = torch.empty((M, H, 2), dtype=torch.float32, device=q.device)
+    lib = _lib.load()
+    ws_bytes = lib.psa_attention_workspace_bytes(nnz, H, F)
+    ws = _workspace(ws_bytes, q.device) if ws_bytes else None
+    with _on(q.device):
+        check(lib.psa_attention_fw(_ptr(rowptr), _ptr(col), _ptr(q), _ptr(k), _ptr(v), _ptr(bias), _bias_heads(bias),
+                                   scale, M, N, H, K, F, nnz, _ptr(out), _ptr(stat), _ptr(ws), ws_bytes, _stream()))
+    return out, stat
+
+
+def _attention_bw_entries_raw(rowptr, col, q, k, v, bias, scale: float, grad_out, out, stat):
+    """(p [nnz, H], dS = p * (dP - delta) [nnz, H]): the per-entry half of the backward, from the saved {m, l}."""
+    M, H, K = q.shape
+    N, F, nnz = k.shape[0], v.shape[2], col.numel()
+    if K % 4 == 0 and F % 4 == 0:
+        grad_out = _aligned16(grad_out)
+    p = torch.empty((nnz, H), dtype=torch.float32, device=q.device)
+    ds = torch.empty((nnz, H), dtype=torch.float32, device=q.device)
+    lib = _lib.load()
+    ws_bytes = lib.psa_attention_workspace_bytes(nnz, H, F)
+    ws = _workspace(ws_bytes, q.device) if ws_bytes else None
+    with _on(q.device):
+        check(lib.psa_attention_bw_entries(_ptr(rowptr), _ptr(col), _ptr(q), _ptr(k), _ptr(v), _ptr(bias),
+                                           _bias_heads(bias), scale, _ptr(grad_out), _ptr(out), _ptr(stat), M, N, H, K,
+                                           F, nnz, _ptr(p), _ptr(ds), _ptr(ws), ws_bytes, _stream()))
+    return p, ds
+
+
+def attention_raw(rowptr, col, q, k, v, bias=None, scale: float = 1.0):
+    """The forward alone, without autograd: (out, stat) with stat [M, H, 2] = {m, l} (2-D operands: [M, 2])."""
+    rowptr, col, q, k, v, bias, _, flat = _attention_operands(rowptr, col, q, k, v, bias)
+    out, stat = _attention_fw_raw(rowptr, col, q.detach(), k.detach(), v.detach(),
+                                  None if bias is None else bias.detach(), float(scale))
+    return (out[:, 0], stat[:, 0]) if flat else (out, stat)
+
+
+def attention_bw(rowptr, col, q, k, v, bias, scale: float, grad_out, out, stat, csc=None,
+                 want=(True, True, True, True)):
+    """(grad_q, grad_k, grad_v, grad_bias) of attention from what its forward left (heads-form operands, out and
+    stat of attention_raw); None where `want` says so.  p and dS [nnz, H] live only inside this call."""
+    want_q, want_k, want_v, want_b = want
+    grad_out = grad_out.contiguous()
+    p, ds = _attention_bw_entries_raw(rowptr, col, q, k, v, bias, scale, grad_out, out, stat)
+    grad_q = grad_k = grad_v = grad_b = None
+    if want_q:  # grad_q[r, h] = scale * sum over the row's entries of dS[e, h] * k[col[e], h]
+        grad_q = _spmm_heads_raw(rowptr, col, ds, k)
+        if scale != 1.0:
+            grad_q *= scale
+    if want_k or want_v:
+        csc = _csc_view(csc, rowptr, col, k.shape[0])
+        if want_k:  # grad_k[c, h] = scale * sum over the column's entries of dS[e, h] * q[row(e), h]
+            grad_k = _spmm_heads_transposed(csc, ds, q)
+            if scale != 1.0:
+                grad_k *= scale
+        if want_v:  # grad_v[c, h] = sum over the column's entries of p[e, h] * grad_out[row(e), h]
+            grad_v = _spmm_heads_transposed(csc, p, grad_out)
+    if want_b and bias is not None:
+        grad_b = ds.sum(dim=1) if bias.dim() == 1 else ds
+    return grad_q, grad_k, grad_v, grad_b
+
+
+class _Attention(torch.autograd.Function):
+    """Heads-form operands, already checked.  Saves q, k, v, out, stat and the caller's bias: no tensor with nnz
+    rows of its own (the pattern is the caller's and rides on ctx)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, bias, rowptr, col, scale, csc):
+        out, stat = _attention_fw_raw(rowptr, col, q, k, v, bias, scale)
+        ctx.save_for_backward(q, k, v, bias, out, stat)
+        ctx.pattern, ctx.scale, ctx.csc = (rowptr, col), scale, csc
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        q, k, v, bias, out, stat = ctx.saved_tensors
+        rowptr, col = ctx.pattern
+        grads = attention_bw(rowptr, col, q, k, v, bias, ctx.scale, grad, out, stat, ctx.csc,
+                             ctx.needs_input_grad[:4])
+        return grads + (None, None, None, None)
+
+
+def attention(rowptr: torch.Tensor, col: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+              bias: Optional[torch.Tensor] = None, scale: float = 1.0, csc=None) -> torch.Tensor:
+    """f32[M, H, F]: out[r, h, :] = sum over the entries of row r of p[e, h] * v[col[e], h, :], p[., h] the softmax
+    over the row of s[e, h] = scale * <q[row(e), h, :], k[col[e], h, :]> (+ bias[e, h] or bias[e]), with q fp32
+    [M, H, K], k fp32 [N, H, K], v fp32 [N, H, F] and bias fp32 [nnz] or [nnz, H]; 2-D q, k, v are one head and
+    give [M, F].  One pass per row (psa_attention_fw); only {max, sum} per row and head is kept for the backward,
+    which recomputes the scores (psa_attention_bw_entries) and takes the gradients of q, k, v from psa_spmm_heads
+    over the CSR and the CSC view.  Differentiable in q, k, v and bias; `scale` is a float.  `csc` as for sddmm."""
+    rowptr, col, q, k, v, bias, _, flat = _attention_operands(rowptr, col, q, k, v, bias)
+    scale = float(scale)
+    if needs_grad(q) or needs_grad(k) or needs_grad(v) or needs_grad(bias):
+        out = _Attention.apply(q, k, v, bias, rowptr, col, scale, csc)
+    else:
+        out = _attention_fw_raw(rowptr, col, q, k, v, bias, scale)[0]
+    return out[:, 0] if flat else out

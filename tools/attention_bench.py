@@ -22,9 +22,15 @@ model of DESIGN.md section 3.9: the SpMM reads nnz*(8 + 4H + 4HF) and writes M*4
 writes nnz*4H.  A side whose operands or temporaries would not fit the device's free memory is reported as not
 run instead of being tried.
 
-usage: python tools/attention_bench.py [--quick] [--once] [--heads]
+The fused lines (--fused: H = 8 with K = F = 16 and 64, H = 1 with K = F = 64) run SparseTensor.attention beside
+the chain softmax(sddmm(A, q, k)) @ v it restates, forward and forward + backward, the two alternating call by
+call, each with its [min .. max].  Byte model of DESIGN.md section 3.10: the fused forward reads
+nnz*(8 + 4HK + 4HF) and writes M*(4HF + 8H); the chain moves nnz*(8*2 + 4H*6) more.  Under each pair the peak of
+torch.cuda.max_memory_allocated over one forward + backward of each side, above what was allocated before it.
+
+usage: python tools/attention_bench.py [--quick] [--once] [--heads] [--fused]
   --quick  config 3 only;  --once  one call of each of our ops and nothing else (for a kernel trace);
-  --heads  the multi-head lines only"""
+  --heads  the multi-head lines only;  --fused  the fused-attention lines only"""
 import statistics
 import sys
 from pathlib import Path
@@ -184,6 +190,63 @@ def run_heads(N, rowptr, col, row, gen, once):
         torch.cuda.empty_cache()
 
 
+def peak_of(fn) -> float:
+    """GB that one call of fn allocates at its peak above what is allocated now."""
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    base = torch.cuda.memory_allocated(dev)
+    torch.cuda.reset_peak_memory_stats(dev)
+    fn()
+    torch.cuda.synchronize()
+    return (torch.cuda.max_memory_allocated(dev) - base) / 1e9
+
+
+def run_fused(N, rowptr, col, gen, once):
+    nnz = col.numel()
+    A = SparseTensor(rowptr=rowptr, col=col, sparse_sizes=(N, N), is_sorted=True, trust_data=True)
+    A.storage.csr2csc()  # the CSC view of the backward, built once as a training loop has it
+    for H, K in ((8, 16), (8, 64), (1, 64)):
+        F = K
+        dense, edge = N * H * K * 4, nnz * H * 4
+        tag = f"H = {H}, K = F = {K}"
+        if not fits(8 * dense + 2 * edge):  # q, k, v, the upstream gradient, out, three gradients; p and dS
+            print(f"   {tag}: not run, the operands and gradients alone take {8 * dense / 1e9:.0f} GB", flush=True)
+            continue
+        chain_fits = fits(8 * dense + 8 * edge)  # scores, weights, their gradients and the CSC-ordered copies
+        q = torch.randn((N, H, K), generator=gen, device=dev) * 0.125
+        k = torch.randn((N, H, K), generator=gen, device=dev)
+        v = torch.randn((N, H, F), generator=gen, device=dev)
+        go = torch.randn((N, H, F), generator=gen, device=dev)
+
+        def forward(kind, qq=q, kk=k, vv=v):
+            if kind == "fused":
+                return A.attention(qq, kk, vv)
+            return psa.sddmm(A, qq, kk).softmax(dim=1) @ vv
+
+        def step(kind):
+            def run():
+                qq, kk, vv = (t.detach().requires_grad_() for t in (q, k, v))
+                forward(kind, qq, kk, vv).backward(go)
+            return run
+
+        step("fused")()
+        if once:
+            continue
+        if chain_fits:
+            diff = float((forward("fused") - forward("chain")).abs().max())
+            print(f"   {tag}: max |fused - chain| = {diff:.2e}", flush=True)
+        fused_bytes = nnz * (8 + 4 * H * K + 4 * H * F) + N * (4 * H * F + 8 * H)
+        heads_line(f"attention forward, {tag}",
+                   [("fused", lambda: forward("fused")), ("chain", (lambda: forward("chain")) if chain_fits else None)],
+                   fused_bytes)
+        heads_line(f"attention fwd + bwd, {tag}",
+                   [("fused", step("fused")), ("chain", step("chain") if chain_fits else None)])
+        peak_c = f"{peak_of(step('chain')):7.3f} GB" if chain_fits else "not run (memory)"
+        print(f"   {'peak memory of one fwd + bwd':34s} fused {peak_of(step('fused')):7.3f} GB   chain {peak_c}", flush=True)
+        del q, k, v, go
+        torch.cuda.empty_cache()
+
+
 def torch_softmax(v, row, M):
     shape = (M,) + tuple(v.shape[1:])
     m = torch.zeros(shape, device=dev).scatter_reduce(0, row.view((-1,) + (1,) * (v.dim() - 1)).expand_as(v), v, "amax",
@@ -218,7 +281,7 @@ def rmat24():
     return N, rowptr, col
 
 
-def run(name, make, once, heads_only=False):
+def run(name, make, once, heads_only=False, fused_only=False):
     N, rowptr, col = make()
     nnz = col.numel()
     row = ops.ptr2ind(rowptr, nnz)
@@ -226,6 +289,10 @@ def run(name, make, once, heads_only=False):
     print(f"== {name}: {N} x {N}, {nnz} entries, longest row {int(deg.max())}, "
           f"{int((deg > 128).sum())} rows above 128 entries", flush=True)
     gen = torch.Generator(device=dev).manual_seed(9)
+    if fused_only:
+        del row
+        run_fused(N, rowptr, col, gen, once)
+        return
     if heads_only:
         run_heads(N, rowptr, col, row, gen, once)
         return
@@ -291,6 +358,7 @@ if __name__ == "__main__":
     print(f"device: {torch.cuda.get_device_name(dev)}", flush=True)
     once = "--once" in sys.argv
     heads_only = "--heads" in sys.argv
-    run("config-3 shape", config3, once, heads_only)
+    fused_only = "--fused" in sys.argv
+    run("config-3 shape", config3, once, heads_only, fused_only)
     if "--quick" not in sys.argv:
-        run("R-MAT 24", rmat24, once, heads_only)
+        run("R-MAT 24", rmat24, once, heads_only, fused_only)
