@@ -974,6 +974,35 @@ int psa_attention_bw_entries(const int64_t* rowptr, const int64_t* col, const fl
                              int64_t nnz, float* p, float* ds, void* workspace, size_t workspace_bytes,
                              psa_stream_t stream);
 
+/* ---- fused sparse attention with two-byte dense operands.  dtype names the format of q, k, v, out and
+ * grad_out: PSA_BF16 is served, any other code is PSA_ERR_INVALID_ARG.  Semantics, layouts, the
+ * non-finite rule, the long-row plan and the workspace (psa_attention_workspace_bytes(nnz, H, F): the
+ * partials stay fp32) are those of psa_attention_fw / psa_attention_bw_entries.  bias, stat, p and ds are
+ * fp32; every product, the scores, the softmax and the accumulators are fp32 and a bf16 result is
+ * rounded once (nearest even) where it is written: out = round(acc / l).
+ *   psa_attention_half_bw_entries  forms delta from the saved, rounded out.
+ *   psa_spmm_heads_half            value fp32 [nnz, H], mat [N, H, F]:
+ *                                  out[r, h, f] = round(alpha * sum_{e in row r} value[e, h] * mat[col[e], h, f]),
+ *                                  out [M, H, F] fully written; psa_spmm_heads' plan and workspace
+ *                                  (psa_spmm_heads_workspace_bytes(nnz, H, F)).  The gradients of the
+ *                                  attention: grad_q = (ds, k) with alpha = scale over the CSR view,
+ *                                  grad_k = (ds, q) with alpha = scale and grad_v = (p, grad_out) with
+ *                                  alpha = 1 over the CSC view.
+ * 16-byte gathers of 8 elements when K % 8 == 0, F % 8 == 0 (psa_spmm_heads_half: F % 8 == 0) and the
+ * two-byte operands are 16-byte aligned, 2-byte loads otherwise: any 2-byte alignment is accepted. */
+int psa_attention_half_fw(int dtype, const int64_t* rowptr, const int64_t* col, const void* q, const void* k,
+                          const void* v, const float* bias, int64_t bias_heads, float scale, int64_t M, int64_t N,
+                          int64_t H, int64_t K, int64_t F, int64_t nnz, void* out, float* stat, void* workspace,
+                          size_t workspace_bytes, psa_stream_t stream);
+int psa_attention_half_bw_entries(int dtype, const int64_t* rowptr, const int64_t* col, const void* q, const void* k,
+                                  const void* v, const float* bias, int64_t bias_heads, float scale,
+                                  const void* grad_out, const void* out, const float* stat, int64_t M, int64_t N,
+                                  int64_t H, int64_t K, int64_t F, int64_t nnz, float* p, float* ds, void* workspace,
+                                  size_t workspace_bytes, psa_stream_t stream);
+int psa_spmm_heads_half(int dtype, const int64_t* rowptr, const int64_t* col, const float* value, const void* mat,
+                        float alpha, int64_t M, int64_t N, int64_t H, int64_t F, int64_t nnz, void* out,
+                        void* workspace, size_t workspace_bytes, psa_stream_t stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -172,6 +172,14 @@ SIGNATURES = {
     "psa_attention_bw_entries": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float,
                                          c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64,
                                          c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "psa_attention_half_fw": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                      c_float, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                      c_void_p, c_size_t, c_void_p]),
+    "psa_attention_half_bw_entries": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                              c_float, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
+                                              c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "psa_spmm_heads_half": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_int64, c_int64,
+                                    c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

@@ -14,6 +14,12 @@ from psa_spmm_heads over the CSR and the CSC view.  The chain of the three ops s
 Non-finite values: a row and head whose scores hold a NaN, a +inf or nothing but -inf is NaN in
 out[r, h, :]; a -inf score among finite ones has weight exactly 0 (a mask); weight 0 against an
 inf in v is NaN (no zero skipping); a row without entries gives 0.
+
+q, k, v are float32 or bfloat16 (all three alike).  With bfloat16 operands the gathers are half-width
+(csrc/attention_half.hip), every product, the scores, the softmax and the sums stay fp32, and out and
+the gradients of q, k, v come back in bfloat16, each rounded once (the gradients from
+csrc/spmm_heads_half.hip, with `scale` applied before the rounding); the bias, {max, sum} and the
+gradient of the bias stay fp32.
 """
 from __future__ import annotations
 
@@ -25,18 +31,20 @@ from .tensor import SparseTensor
 
 def attention(src: SparseTensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float = 1.0,
               bias: bool = False) -> torch.Tensor:
-    """Dense fp32 [M, H, F] from q fp32 [M, H, K], k fp32 [N, H, K] and v fp32 [N, H, F] over the pattern of
-    `src`; 2-D q [M, K], k [N, K], v [N, F] are one head and give [M, F].  With bias=False the stored values
-    of `src` are NOT read; with bias=True they must be fp32 [nnz] (shared by the heads) or [nnz, H] and are
-    added to the scaled scores (-inf masks an entry).  Differentiable in q, k, v and, when they are tracked,
+    """Dense [M, H, F] from q [M, H, K], k [N, H, K] and v [N, H, F], all float32 or all bfloat16 (the result has
+    their dtype), over the pattern of `src`; 2-D q [M, K], k [N, K], v [N, F] are one head and give [M, F].
+    With bias=False the stored values of `src` are NOT read; with bias=True they must be fp32 [nnz] (shared by the
+    heads) or [nnz, H], for either dtype of q, k, v, and are added to the scaled scores (-inf masks an entry).  Differentiable in q, k, v and, when they are tracked,
     the values; `scale` is a Python float."""
     for name, t in (("q", q), ("k", k), ("v", v)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"attention: {name} must be a torch.Tensor")
-        if t.dtype != torch.float32:
-            raise TypeError(f"attention: {name} must be float32 (got {t.dtype})")
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"attention: {name} must be float32 or bfloat16 (got {t.dtype})")
         if t.dim() not in (2, 3):
             raise ValueError(f"attention: {name} must be 2-D, or 3-D [rows, H, width]")
+    if not (q.dtype == k.dtype == v.dtype):
+        raise TypeError(f"attention: q, k, v must share one dtype (got {q.dtype}, {k.dtype}, {v.dtype})")
     if isinstance(scale, bool) or not isinstance(scale, (int, float)):
         raise TypeError("attention: scale must be a float")
     if not isinstance(bias, bool):

@@ -59,6 +59,18 @@ __device__ __forceinline__ float widen1(const void* p, int64_t i) {
   else return __half2float(*reinterpret_cast<const __half*>(&h));
 }
 
+// one fp32 -> one 2-byte float, round to nearest even
+template <typename T>
+__device__ __forceinline__ uint16_t narrow1(float f) {
+  if constexpr (std::is_same<T, BF16>::value) {
+    const __hip_bfloat16 h = __float2bfloat16(f);
+    return *reinterpret_cast<const uint16_t*>(&h);
+  } else {
+    const __half h = __float2half_rn(f);
+    return *reinterpret_cast<const uint16_t*>(&h);
+  }
+}
+
 __device__ __forceinline__ int64_t shfl_i64(int64_t x, int src) {
   return __shfl(static_cast<long long>(x), src);
 }

@@ -1736,6 +1736,34 @@ def _spmm_heads_raw(rowptr: torch.Tensor, col: torch.Tensor, value: torch.Tensor
     return out
 
 
+def spmm_heads_half_raw(rowptr: torch.Tensor, col: torch.Tensor, value: torch.Tensor, mat: torch.Tensor,
+                        alpha: float = 1.0) -> torch.Tensor:
+    """bf16[M, H, F] = round(alpha * sum over the entries of row r of value[e, h] * mat[col[e], h, :]) with value
+    fp32 [nnz, H] and mat bf16 [N, H, F]: fp32 products and sums, one rounding (psa_spmm_heads_half).  A raw call
+    without autograd: the backward of the bf16 attention takes its three gradients from it."""
+    rowptr, col, M, nnz = _heads_pattern(rowptr, col)
+    value = _f32(value, "value")
+    _gpu(mat, "mat")
+    if mat.dtype != torch.bfloat16:
+        raise TypeError(f"mat must be bfloat16 (got {mat.dtype})")
+    if mat.dim() != 3:
+        raise ValueError(f"spmm over per-head values: the dense operand must be [N, H, F] (got {tuple(mat.shape)})")
+    mat = mat.contiguous()
+    N, H, F = mat.shape
+    if value.dim() != 2 or value.shape[0] != nnz or value.shape[1] != H:
+        raise ValueError(f"spmm over per-head values: value must be [{nnz}, {H}] (got {tuple(value.shape)})")
+    if F % 8 == 0:  # the 16-byte gathers; other F (and views) take the 2-byte form
+        mat = _aligned16(mat)
+    out = torch.empty((M, H, F), dtype=mat.dtype, device=mat.device)
+    lib = _lib.load()
+    ws_bytes = lib.psa_spmm_heads_workspace_bytes(nnz, H, F)  # the partials are fp32
+    ws = _workspace(ws_bytes, mat.device) if ws_bytes else None
+    with _on(mat.device):
+        check(lib.psa_spmm_heads_half(_DTYPE_ID[mat.dtype], _ptr(rowptr), _ptr(col), _ptr(value), _ptr(mat),
+                                      float(alpha), M, N, H, F, nnz, _ptr(out), _ptr(ws), ws_bytes, _stream()))
+    return out
+
+
 def _sddmm_heads_raw(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     rowptr, col, M, nnz = _heads_pattern(rowptr, col)
     x, y = _f32(x, "x"), _f32(y, "y")
@@ -1805,7 +1833,9 @@ def _attention_operands(rowptr, col, q, k, v, bias):
     """The checked, contiguous operands in heads form, plus (M, N, H, K, F, nnz) and whether the caller gave the
     2-D form."""
     rowptr, col, M, nnz = _heads_pattern(rowptr, col)
-    q, k, v = _f32(q, "q"), _f32(k, "k"), _f32(v, "v")
+    q, k, v = _attention_dense(q, "q"), _attention_dense(k, "k"), _attention_dense(v, "v")
+    if not (q.dtype == k.dtype == v.dtype):
+        raise TypeError(f"attention: q, k, v must share one dtype (got {q.dtype}, {k.dtype}, {v.dtype})")
     dims = {q.dim(), k.dim(), v.dim()}
     if dims not in ({2}, {3}):
         raise ValueError(f"attention: q, k, v must all be 2-D, or all 3-D [rows, H, width] "
@@ -1824,9 +1854,21 @@ def _attention_operands(rowptr, col, q, k, v, bias):
         bias = _f32(bias, "bias")
         if bias.shape not in ((nnz,), (nnz, H)):
             raise ValueError(f"attention: bias must be [{nnz}] or [{nnz}, {H}] (got {tuple(bias.shape)})")
-    if K % 4 == 0 and F % 4 == 0:  # the 16-byte form; other widths (and views) take the 4-byte form
+    if K % _vec16(q) == 0 and F % _vec16(q) == 0:  # the 16-byte form; other widths (and views) take the element form
         q, k, v = _aligned16(q), _aligned16(k), _aligned16(v)
     return rowptr, col, q, k, v, bias, (M, N, H, K, F, nnz), flat
+
+
+def _attention_dense(x: torch.Tensor, name: str) -> torch.Tensor:
+    _gpu(x, name)
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{name} must be float32 or bfloat16 (got {x.dtype})")
+    return x.contiguous()
+
+
+def _vec16(x: torch.Tensor) -> int:
+    """Elements of x's dtype in one 16-byte load: 4 fp32, 8 bf16."""
+    return 16 // x.element_size()
 
 
 def _bias_heads(bias: Optional[torch.Tensor]) -> int:
@@ -1837,14 +1879,20 @@ def _attention_fw_raw(rowptr, col, q, k, v, bias, scale: float):
     """(out [M, H, F], stat [M, H, 2] = {row maximum, sum of exp(s - maximum)}) from checked heads-form operands."""
     M, H, K = q.shape
     N, F, nnz = k.shape[0], v.shape[2], col.numel()
-    out = torch.empty((M, H, F), dtype=torch.float32, device=q.device)
+    out = torch.empty((M, H, F), dtype=q.dtype, device=q.device)
     stat = torch.empty((M, H, 2), dtype=torch.float32, device=q.device)
     lib = _lib.load()
-    ws_bytes = lib.psa_attention_workspace_bytes(nnz, H, F)
+    ws_bytes = lib.psa_attention_workspace_bytes(nnz, H, F)  # the partials are fp32 for either dtype
     ws = _workspace(ws_bytes, q.device) if ws_bytes else None
     with _on(q.device):
-        check(lib.psa_attention_fw(_ptr(rowptr), _ptr(col), _ptr(q), _ptr(k), _ptr(v), _ptr(bias), _bias_heads(bias),
-                                   scale, M, N, H, K, F, nnz, _ptr(out), _ptr(stat), _ptr(ws), ws_bytes, _stream()))
+        if q.dtype == torch.float32:
+            check(lib.psa_attention_fw(_ptr(rowptr), _ptr(col), _ptr(q), _ptr(k), _ptr(v), _ptr(bias),
+                                       _bias_heads(bias), scale, M, N, H, K, F, nnz, _ptr(out), _ptr(stat), _ptr(ws),
+                                       ws_bytes, _stream()))
+        else:
+            check(lib.psa_attention_half_fw(_DTYPE_ID[q.dtype], _ptr(rowptr), _ptr(col), _ptr(q), _ptr(k), _ptr(v),
+                                            _ptr(bias), _bias_heads(bias), scale, M, N, H, K, F, nnz, _ptr(out),
+                                            _ptr(stat), _ptr(ws), ws_bytes, _stream()))
     return out, stat
 
 
@@ -1852,7 +1900,9 @@ def _attention_bw_entries_raw(rowptr, col, q, k, v, bias, scale: float, grad_out
     """(p [nnz, H], dS = p * (dP - delta) [nnz, H]): the per-entry half of the backward, from the saved {m, l}."""
     M, H, K = q.shape
     N, F, nnz = k.shape[0], v.shape[2], col.numel()
-    if K % 4 == 0 and F % 4 == 0:
+    if grad_out.dtype != q.dtype:
+        raise TypeError(f"attention: grad_out must be {q.dtype} as q, k, v (got {grad_out.dtype})")
+    if K % _vec16(q) == 0 and F % _vec16(q) == 0:
         grad_out = _aligned16(grad_out)
     p = torch.empty((nnz, H), dtype=torch.float32, device=q.device)
     ds = torch.empty((nnz, H), dtype=torch.float32, device=q.device)
@@ -1860,9 +1910,15 @@ def _attention_bw_entries_raw(rowptr, col, q, k, v, bias, scale: float, grad_out
     ws_bytes = lib.psa_attention_workspace_bytes(nnz, H, F)
     ws = _workspace(ws_bytes, q.device) if ws_bytes else None
     with _on(q.device):
-        check(lib.psa_attention_bw_entries(_ptr(rowptr), _ptr(col), _ptr(q), _ptr(k), _ptr(v), _ptr(bias),
-                                           _bias_heads(bias), scale, _ptr(grad_out), _ptr(out), _ptr(stat), M, N, H, K,
-                                           F, nnz, _ptr(p), _ptr(ds), _ptr(ws), ws_bytes, _stream()))
+        if q.dtype == torch.float32:
+            check(lib.psa_attention_bw_entries(_ptr(rowptr), _ptr(col), _ptr(q), _ptr(k), _ptr(v), _ptr(bias),
+                                               _bias_heads(bias), scale, _ptr(grad_out), _ptr(out), _ptr(stat), M, N, H,
+                                               K, F, nnz, _ptr(p), _ptr(ds), _ptr(ws), ws_bytes, _stream()))
+        else:
+            check(lib.psa_attention_half_bw_entries(_DTYPE_ID[q.dtype], _ptr(rowptr), _ptr(col), _ptr(q), _ptr(k),
+                                                    _ptr(v), _ptr(bias), _bias_heads(bias), scale, _ptr(grad_out),
+                                                    _ptr(out), _ptr(stat), M, N, H, K, F, nnz, _ptr(p), _ptr(ds),
+                                                    _ptr(ws), ws_bytes, _stream()))
     return p, ds
 
 
@@ -1882,6 +1938,18 @@ def attention_bw(rowptr, col, q, k, v, bias, scale: float, grad_out, out, stat, 
     grad_out = grad_out.contiguous()
     p, ds = _attention_bw_entries_raw(rowptr, col, q, k, v, bias, scale, grad_out, out, stat)
     grad_q = grad_k = grad_v = grad_b = None
+    if q.dtype != torch.float32:  # psa_spmm_heads_half: fp32 sums, scale before the one rounding, no fp32 copies
+        if want_q:
+            grad_q = spmm_heads_half_raw(rowptr, col, ds, k, scale)
+        if want_k or want_v:
+            colptr, row_csc, csr2csc = _csc_view(csc, rowptr, col, k.shape[0])
+            if want_k:
+                grad_k = spmm_heads_half_raw(colptr, row_csc, _gather_rows_raw(ds, csr2csc), q, scale)
+            if want_v:
+                grad_v = spmm_heads_half_raw(colptr, row_csc, _gather_rows_raw(p, csr2csc), grad_out, 1.0)
+        if want_b and bias is not None:
+            grad_b = ds.sum(dim=1) if bias.dim() == 1 else ds
+        return grad_q, grad_k, grad_v, grad_b
     if want_q:  # grad_q[r, h] = scale * sum over the row's entries of dS[e, h] * k[col[e], h]
         grad_q = _spmm_heads_raw(rowptr, col, ds, k)
         if scale != 1.0:
@@ -1921,12 +1989,15 @@ class _Attention(torch.autograd.Function):
 
 def attention(rowptr: torch.Tensor, col: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
               bias: Optional[torch.Tensor] = None, scale: float = 1.0, csc=None) -> torch.Tensor:
-    """f32[M, H, F]: out[r, h, :] = sum over the entries of row r of p[e, h] * v[col[e], h, :], p[., h] the softmax
-    over the row of s[e, h] = scale * <q[row(e), h, :], k[col[e], h, :]> (+ bias[e, h] or bias[e]), with q fp32
-    [M, H, K], k fp32 [N, H, K], v fp32 [N, H, F] and bias fp32 [nnz] or [nnz, H]; 2-D q, k, v are one head and
-    give [M, F].  One pass per row (psa_attention_fw); only {max, sum} per row and head is kept for the backward,
-    which recomputes the scores (psa_attention_bw_entries) and takes the gradients of q, k, v from psa_spmm_heads
-    over the CSR and the CSC view.  Differentiable in q, k, v and bias; `scale` is a float.  `csc` as for sddmm."""
+    """[M, H, F]: out[r, h, :] = sum over the entries of row r of p[e, h] * v[col[e], h, :], p[., h] the softmax
+    over the row of s[e, h] = scale * <q[row(e), h, :], k[col[e], h, :]> (+ bias[e, h] or bias[e]), with q
+    [M, H, K], k [N, H, K], v [N, H, F] all float32 or all bfloat16 and bias fp32 [nnz] or [nnz, H]; 2-D q, k, v
+    are one head and give [M, F].  One pass per row (psa_attention_fw); only {max, sum} per row and head is kept
+    for the backward, which recomputes the scores (psa_attention_bw_entries) and takes the gradients of q, k, v
+    from psa_spmm_heads over the CSR and the CSC view.  bfloat16 operands (psa_attention_half_fw /
+    _bw_entries / psa_spmm_heads_half) give a bfloat16 out and bfloat16 gradients: gathers are half-width,
+    all arithmetic, stat and grad_bias are fp32, each bfloat16 result is rounded once.  Differentiable in
+    q, k, v and bias; `scale` is a float.  `csc` as for sddmm."""
     rowptr, col, q, k, v, bias, _, flat = _attention_operands(rowptr, col, q, k, v, bias)
     scale = float(scale)
     if needs_grad(q) or needs_grad(k) or needs_grad(v) or needs_grad(bias):

@@ -28,9 +28,16 @@ call, each with its [min .. max].  Byte model of DESIGN.md section 3.10: the fus
 nnz*(8 + 4HK + 4HF) and writes M*(4HF + 8H); the chain moves nnz*(8*2 + 4H*6) more.  Under each pair the peak of
 torch.cuda.max_memory_allocated over one forward + backward of each side, above what was allocated before it.
 
-usage: python tools/attention_bench.py [--quick] [--once] [--heads] [--fused]
+With --dtype bf16 the fused lines run SparseTensor.attention on bfloat16 q, k, v beside the same op on the fp32
+values they were rounded from (the yardstick), the two alternating call by call in the same run, forward and
+forward + backward, each with its [min .. max]: a difference counts only where it exceeds that spread.  Byte model
+of DESIGN.md section 3.11 for the bf16 forward: reads nnz*(8 + 2HK + 2HF), writes M*(2HF + 8H).  Under each pair
+the peak memory of one forward + backward of each side.
+
+usage: python tools/attention_bench.py [--quick] [--once] [--heads] [--fused [--dtype bf16]]
   --quick  config 3 only;  --once  one call of each of our ops and nothing else (for a kernel trace);
-  --heads  the multi-head lines only;  --fused  the fused-attention lines only"""
+  --heads  the multi-head lines only;  --fused  the fused-attention lines only;
+  --dtype bf16  (with --fused) the bf16 fused op beside the fp32 fused op"""
 import statistics
 import sys
 from pathlib import Path
@@ -247,6 +254,51 @@ def run_fused(N, rowptr, col, gen, once):
         torch.cuda.empty_cache()
 
 
+def run_fused_bf16(N, rowptr, col, gen, once):
+    """The bf16 fused op ("ours" of each line) beside the fp32 fused op on the same shapes."""
+    nnz = col.numel()
+    A = SparseTensor(rowptr=rowptr, col=col, sparse_sizes=(N, N), is_sorted=True, trust_data=True)
+    A.storage.csr2csc()  # the CSC view of the backward, built once as a training loop has it
+    for H, K in ((8, 16), (8, 64), (1, 64)):
+        F = K
+        dense, edge = N * H * K * 4, nnz * H * 4
+        tag = f"H = {H}, K = F = {K}"
+        if not fits(12 * dense + 2 * edge):  # both sides' operands, upstream gradient, out and gradients; p and dS
+            print(f"   {tag}: not run, the operands and gradients alone take {12 * dense / 1e9:.0f} GB", flush=True)
+            continue
+        sides = {"bf16": tuple(t.to(torch.bfloat16) for t in (
+            torch.randn((N, H, K), generator=gen, device=dev) * 0.125, torch.randn((N, H, K), generator=gen, device=dev),
+            torch.randn((N, H, F), generator=gen, device=dev), torch.randn((N, H, F), generator=gen, device=dev)))}
+        sides["fp32"] = tuple(t.float() for t in sides["bf16"])  # the same values on both sides
+
+        def forward(name):
+            q, k, v, _ = sides[name]
+            return A.attention(q, k, v)
+
+        def step(name):
+            def run():
+                q, k, v, go = sides[name]
+                qq, kk, vv = (t.detach().requires_grad_() for t in (q, k, v))
+                A.attention(qq, kk, vv).backward(go)
+            return run
+
+        step("bf16")()
+        if once:
+            continue
+        ref = forward("fp32")
+        diff = float(((forward("bf16").float() - ref).abs() / ref.abs().clamp_min(1e-3)).max())
+        print(f"   {tag}: max |bf16 - fp32| / max(|fp32|, 1e-3) = {diff:.2e}", flush=True)
+        del ref
+        half_bytes = nnz * (8 + 2 * H * K + 2 * H * F) + N * (2 * H * F + 8 * H)
+        heads_line(f"attention forward, {tag}", [("bf16", lambda: forward("bf16")), ("fp32", lambda: forward("fp32"))],
+                   half_bytes)
+        heads_line(f"attention fwd + bwd, {tag}", [("bf16", step("bf16")), ("fp32", step("fp32"))])
+        print(f"   {'peak memory of one fwd + bwd':34s} bf16 {peak_of(step('bf16')):7.3f} GB   "
+              f"fp32 {peak_of(step('fp32')):7.3f} GB", flush=True)
+        del sides
+        torch.cuda.empty_cache()
+
+
 def torch_softmax(v, row, M):
     shape = (M,) + tuple(v.shape[1:])
     m = torch.zeros(shape, device=dev).scatter_reduce(0, row.view((-1,) + (1,) * (v.dim() - 1)).expand_as(v), v, "amax",
@@ -281,7 +333,7 @@ def rmat24():
     return N, rowptr, col
 
 
-def run(name, make, once, heads_only=False, fused_only=False):
+def run(name, make, once, heads_only=False, fused_only=False, half=False):
     N, rowptr, col = make()
     nnz = col.numel()
     row = ops.ptr2ind(rowptr, nnz)
@@ -291,7 +343,7 @@ def run(name, make, once, heads_only=False, fused_only=False):
     gen = torch.Generator(device=dev).manual_seed(9)
     if fused_only:
         del row
-        run_fused(N, rowptr, col, gen, once)
+        (run_fused_bf16 if half else run_fused)(N, rowptr, col, gen, once)
         return
     if heads_only:
         run_heads(N, rowptr, col, row, gen, once)
@@ -359,6 +411,12 @@ if __name__ == "__main__":
     once = "--once" in sys.argv
     heads_only = "--heads" in sys.argv
     fused_only = "--fused" in sys.argv
-    run("config-3 shape", config3, once, heads_only, fused_only)
+    half = False
+    if "--dtype" in sys.argv:
+        dtype = sys.argv[sys.argv.index("--dtype") + 1:][:1]
+        if dtype not in (["bf16"], ["fp32"]) or not fused_only:
+            sys.exit("--dtype takes bf16 or fp32 and goes with --fused")
+        half = dtype == ["bf16"]
+    run("config-3 shape", config3, once, heads_only, fused_only, half)
     if "--quick" not in sys.argv:
-        run("R-MAT 24", rmat24, once, heads_only, fused_only)
+        run("R-MAT 24", rmat24, once, heads_only, fused_only, half)
