@@ -1003,6 +1003,57 @@ int psa_spmm_heads_half(int dtype, const int64_t* rowptr, const int64_t* col, co
                         float alpha, int64_t M, int64_t N, int64_t H, int64_t F, int64_t nnz, void* out,
                         void* workspace, size_t workspace_bytes, psa_stream_t stream);
 
+/* ---- fused sparse attention with dropout of the attention weights, fp32 and two-byte operands: the
+ * four entry points above with `double dropout_p, uint64_t seed` after scale.  Everything not said
+ * here is as there: s, p = softmax_row(s) and stat = {m, l} do not change (dropout comes after the
+ * softmax), nor do the layouts, the forms, the long-row plan and the workspace
+ * (psa_attention_workspace_bytes).
+ *   T          = floor(dropout_p * 2^24)                     (in double; 0 <= dropout_p < 1, anything
+ *                                                             else, NaN included, is PSA_ERR_INVALID_ARG)
+ *   r(e, h)    = mix64(rand_stream(seed, e) + h)             (csrc/rng.h; e = position of the entry in
+ *                                                             CSR order, h = absolute head, uint64 wrap)
+ *   keep(e, h) = (r(e, h) >> 40) >= T
+ *   inv_keep   = float32(1 / (1 - dropout_p))
+ *   out[r, h, :] = inv_keep * sum_{e in row r} keep(e, h) * p[e, h] * v[col[e], h, :]
+ * The mask depends on (seed, e, h) only: not on head blocks, chunks, the load width, the dtype or
+ * forward versus backward, so the fp32 and bf16 entry points drop the same entries for one seed and
+ * a host restatement reproduces it bit for bit.  It is evaluated once per (entry, head) and never
+ * stored; the seed is a launch argument, so a captured graph replays the same mask.  keep multiplies
+ * the weight inside the sum (exact); inv_keep is applied once per output element after the division
+ * by l, in fp32 (bf16: before the one rounding), by the row kernel and by the long-row combine.
+ * dropout_p = 0 keeps everything and multiplies by 1: the bits of the plain entry points.
+ *   psa_attention_dropout_bw_entries  with D = keep * inv_keep: dP = D * <grad_out, v>, delta =
+ *                                     <grad_out, out> (out carries D), ds = p * (dP - delta), and
+ *                                     p * D is written where p was, so that grad_v = (p, grad_out)
+ *                                     over the CSC view needs nothing else.
+ * Non-finite values by plain IEEE arithmetic: a dropped entry has weight exactly 0 and 0 against an
+ * inf in v is NaN (no zero skipping); a NaN score poisons l whether or not its entry is dropped.
+ *   psa_attention_dropout_mask        mask[e * H + h] = keep(e, h) as bytes (0 / 1), [nnz, H], fully
+ *                                     written: the same mask for the unfused chain. */
+int psa_attention_dropout_fw(const int64_t* rowptr, const int64_t* col, const float* q, const float* k, const float* v,
+                             const float* bias, int64_t bias_heads, float scale, double dropout_p, uint64_t seed,
+                             int64_t M, int64_t N, int64_t H, int64_t K, int64_t F, int64_t nnz, float* out,
+                             float* stat, void* workspace, size_t workspace_bytes, psa_stream_t stream);
+int psa_attention_dropout_bw_entries(const int64_t* rowptr, const int64_t* col, const float* q, const float* k,
+                                     const float* v, const float* bias, int64_t bias_heads, float scale,
+                                     double dropout_p, uint64_t seed, const float* grad_out, const float* out,
+                                     const float* stat, int64_t M, int64_t N, int64_t H, int64_t K, int64_t F,
+                                     int64_t nnz, float* p, float* ds, void* workspace, size_t workspace_bytes,
+                                     psa_stream_t stream);
+int psa_attention_half_dropout_fw(int dtype, const int64_t* rowptr, const int64_t* col, const void* q, const void* k,
+                                  const void* v, const float* bias, int64_t bias_heads, float scale, double dropout_p,
+                                  uint64_t seed, int64_t M, int64_t N, int64_t H, int64_t K, int64_t F, int64_t nnz,
+                                  void* out, float* stat, void* workspace, size_t workspace_bytes,
+                                  psa_stream_t stream);
+int psa_attention_half_dropout_bw_entries(int dtype, const int64_t* rowptr, const int64_t* col, const void* q,
+                                          const void* k, const void* v, const float* bias, int64_t bias_heads,
+                                          float scale, double dropout_p, uint64_t seed, const void* grad_out,
+                                          const void* out, const float* stat, int64_t M, int64_t N, int64_t H,
+                                          int64_t K, int64_t F, int64_t nnz, float* p, float* ds, void* workspace,
+                                          size_t workspace_bytes, psa_stream_t stream);
+int psa_attention_dropout_mask(int64_t nnz, int64_t H, double dropout_p, uint64_t seed, uint8_t* mask,
+                               psa_stream_t stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -6,7 +6,7 @@ ops fails loudly — there is no CPU or eager fallback anywhere in this package.
 from __future__ import annotations
 
 import ctypes
-from ctypes import c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p, c_char_p
+from ctypes import c_double, c_float, c_int, c_int64, c_size_t, c_uint64, c_void_p, c_char_p
 from pathlib import Path
 
 # The framework must bring its HIP runtime into the process FIRST: the core
@@ -180,6 +180,22 @@ SIGNATURES = {
                                               c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "psa_spmm_heads_half": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_int64, c_int64,
                                     c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # the dropout forms: (double dropout_p, uint64_t seed) after scale
+    "psa_attention_dropout_fw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float,
+                                         c_double, c_uint64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "psa_attention_dropout_bw_entries": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                                 c_float, c_double, c_uint64, c_void_p, c_void_p, c_void_p, c_int64,
+                                                 c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                                 c_void_p, c_size_t, c_void_p]),
+    "psa_attention_half_dropout_fw": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                              c_float, c_double, c_uint64, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                              c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "psa_attention_half_dropout_bw_entries": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_int64, c_float, c_double, c_uint64, c_void_p, c_void_p,
+                                                      c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "psa_attention_dropout_mask": (c_int, [c_int64, c_int64, c_double, c_uint64, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -6,6 +6,8 @@
 //   psa_attention_half_fw          out bf16 [M, H, F] = round(acc / l) and stat fp32 [M, H, 2] = {m, l}
 //   psa_attention_half_bw_entries  p and dS = p * (dP - delta) fp32 [nnz, H]; delta = <grad_out, out> is taken
 //                                  from the saved, rounded out
+//   psa_attention_half_dropout_fw / _bw_entries  the same with dropout of the weights (attention_dropout.h):
+//                                  inv_keep is applied in fp32 before the one rounding
 //
 // Plan (attention.hip, unchanged): one wave per CSR row, 64-entry tiles, scores through the per-wave LDS tile
 // of 64 x Hb floats, online softmax per lane group, rows above psa::kLongRow entries as 128-entry chunks whose
@@ -23,6 +25,7 @@
 // Non-finite values, reproducibility and capture as attention.hip: plain IEEE arithmetic, expf, no float
 // atomics, no host read.  Every address is formed in 64-bit arithmetic.
 #include "common.h"
+#include "attention_dropout.h"
 #include "half_rows.h"
 #include "long_rows.h"
 
@@ -185,6 +188,14 @@ struct FwArgs {
   DotGeo dot;   // scores
   int P, shift;  // lanes per entry in the aggregation
   int ntiles;   // tiles of P * VEC elements over Hb * F
+  static constexpr bool kDrop = false;
+};
+
+// The dropout forms of the kernels take their arguments with the mask's parameters behind them; the plain
+// forms never see them (every use sits under if constexpr (A::kDrop)).
+struct FwDropArgs : FwArgs {
+  static constexpr bool kDrop = true;
+  psa::Drop drop;
 };
 
 // {m, l} of two disjoint sets of entries and the factors that bring their sums to the common maximum.
@@ -201,9 +212,12 @@ __device__ __forceinline__ float merge_sum(float a, float fa, float b, float fb)
 
 // {m, l, acc} of the entries [s, e) of one row for the NT tiles from tile0 on of head block hb, merged over
 // the lane groups: every lane ends with the fp32 state of the elements it owns.
-template <typename T, int VEC, int NR, int NT>
-__device__ __forceinline__ void attn_range(const FwArgs& a, int64_t row, int hb, int Hs, int tile0, int64_t s,
-                                           int64_t e, int lane, float* __restrict__ tile, float (&m)[NT],
+// Dropout: keeps[h] holds the keep bits of the tile's 64 entries for head h of the block; a dropped entry
+// counts in l and adds an exact 0 * v to acc.
+template <class A, typename T, int VEC, int NR, int NT>
+__device__ __forceinline__ void attn_range(const A& a, int64_t row, int hb, int Hs, int tile0, int64_t s,
+                                           int64_t e, int lane, float* __restrict__ tile,
+                                           unsigned long long* __restrict__ keeps, float (&m)[NT],
                                            float (&l)[NT], float (&acc)[NT][VEC]) {
   constexpr int U = kMaxTiles / NT;  // entries in flight per lane
   const int grp = lane >> a.shift;
@@ -238,10 +252,17 @@ __device__ __forceinline__ void attn_range(const FwArgs& a, int64_t row, int hb,
     wave_sync();  // the previous tile has been consumed
     dots_tile<T, VEC, NR>(kb, qrow, xr, a.dot, Hs, c_l, n, lane, a.scale,
                           biasb ? biasb + base * a.bias_heads : nullptr, a.bias_heads, bhstep, tile, a.Hb);
+    if constexpr (A::kDrop) {  // one draw per (entry, head): lane i draws for entry base + i, a ballot per head
+      const uint64_t stream = psa::rand_stream(a.drop.seed, base + lane);
+      for (int h = 0; h < Hs; ++h) {
+        const unsigned long long bits = __ballot(psa::keep_of(stream, static_cast<int64_t>(hb) + h, a.drop.T));
+        if (lane == 0) keeps[h] = bits;
+      }
+    }
     wave_sync();
     for (int j = 0; j < n; j += G * U) {
       float b[U][NT][VEC], sc[U][NT];
-      bool ok[U];
+      bool ok[U], kept[U][NT];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int idx = j + u * G + grp;
@@ -250,10 +271,12 @@ __device__ __forceinline__ void attn_range(const FwArgs& a, int64_t row, int hb,
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
           sc[u][t] = 0.f;
+          kept[u][t] = true;
 #pragma unroll
           for (int i = 0; i < VEC; ++i) b[u][t][i] = 0.f;
           if (ok[u] && act[t]) {
             sc[u][t] = tile[idx * a.Hb + hd[t]];
+            if constexpr (A::kDrop) kept[u][t] = (keeps[hd[t]] >> idx) & 1ull;
             load_vec<T, VEC>(vb + c * vstride + d[t], b[u][t]);
           }
         }
@@ -274,8 +297,9 @@ __device__ __forceinline__ void attn_range(const FwArgs& a, int64_t row, int hb,
             // nothing but -inf so far: against 0, so that -inf adds an exact 0 and a NaN stays a NaN
             const float w = expf(sc[u][t] - (mn == neg_inf() ? 0.f : mn));
             l[t] += w;
+            const float wk = kept[u][t] ? w : 0.f;
 #pragma unroll
-            for (int i = 0; i < VEC; ++i) acc[t][i] += w * b[u][t][i];
+            for (int i = 0; i < VEC; ++i) acc[t][i] += wk * b[u][t][i];
           }
         }
       }
@@ -300,9 +324,10 @@ __device__ __forceinline__ void attn_range(const FwArgs& a, int64_t row, int hb,
 
 // All head blocks and tiles of the range [s, e) of one row into dst[0 .. H * F) and sdst[0 .. 2 * H):
 // the row itself (NORMALISE: dst is elements, round(acc / l)) or a chunk's partial (dst is floats, acc as it is).
-template <typename T, int VEC, int NR, int NT, bool NORMALISE>
-__device__ __forceinline__ void attn_row(const FwArgs& a, int64_t row, int64_t s, int64_t e, int lane,
-                                         float* __restrict__ tile, void* __restrict__ dst, float* __restrict__ sdst) {
+template <class A, typename T, int VEC, int NR, int NT, bool NORMALISE>
+__device__ __forceinline__ void attn_row(const A& a, int64_t row, int64_t s, int64_t e, int lane,
+                                         float* __restrict__ tile, unsigned long long* __restrict__ keeps,
+                                         void* __restrict__ dst, float* __restrict__ sdst) {
   const int grp = lane >> a.shift;
   const int p = lane & (a.P - 1);
   for (int64_t hb = 0; hb < a.H; hb += a.Hb) {
@@ -310,7 +335,7 @@ __device__ __forceinline__ void attn_row(const FwArgs& a, int64_t row, int64_t s
     const int64_t Ds = static_cast<int64_t>(Hs) * a.F;
     for (int tile0 = 0; tile0 < a.ntiles; tile0 += NT) {
       float m[NT], l[NT], acc[NT][VEC];
-      attn_range<T, VEC, NR, NT>(a, row, static_cast<int>(hb), Hs, tile0, s, e, lane, tile, m, l, acc);
+      attn_range<A, T, VEC, NR, NT>(a, row, static_cast<int>(hb), Hs, tile0, s, e, lane, tile, keeps, m, l, acc);
       if (grp == 0) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
@@ -319,6 +344,10 @@ __device__ __forceinline__ void attn_row(const FwArgs& a, int64_t row, int64_t s
             if constexpr (NORMALISE) {
 #pragma unroll
               for (int i = 0; i < VEC; ++i) acc[t][i] = acc[t][i] / l[t];
+              if constexpr (A::kDrop) {  // once per output element, after the division
+#pragma unroll
+                for (int i = 0; i < VEC; ++i) acc[t][i] = __fmul_rn(acc[t][i], a.drop.inv_keep);
+              }
               store_vec<T, VEC>(static_cast<elem_t*>(dst) + hb * a.F + d, acc[t]);
             } else {
               store_f32<VEC>(static_cast<float*>(dst) + hb * a.F + d, acc[t]);
@@ -335,11 +364,20 @@ __device__ __forceinline__ void attn_row(const FwArgs& a, int64_t row, int64_t s
   }
 }
 
-template <typename T, int VEC, int NR, int NT>
+// The dropout forms keep their keep bits (kHeadBlock x 64 bits per wave) behind the wave's tile.
+template <class A>
+constexpr int tile_floats() { return 64 * kHeadBlock + (A::kDrop ? 2 * kHeadBlock : 0); }
+
+template <class A>
+__device__ __forceinline__ unsigned long long* keeps_of(float* tile) {
+  return reinterpret_cast<unsigned long long*>(tile + 64 * kHeadBlock);  // 4096 bytes in: 8-byte aligned
+}
+
+template <class A, typename T, int VEC, int NR, int NT>
 __global__ void __launch_bounds__(kThreads)
-attn_half_fw_kernel(const FwArgs a, elem_t* __restrict__ out, float* __restrict__ stat,
+attn_half_fw_kernel(const A a, elem_t* __restrict__ out, float* __restrict__ stat,
                     unsigned long long* __restrict__ long_ctr, psa::LongEntry* __restrict__ long_list) {
-  __shared__ float tiles[kWaves][64 * kHeadBlock];
+  __shared__ float tiles[kWaves][tile_floats<A>()];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t row = static_cast<int64_t>(blockIdx.x) * kWaves + wave;
@@ -361,16 +399,16 @@ attn_half_fw_kernel(const FwArgs a, elem_t* __restrict__ out, float* __restrict_
     }
     return;
   }
-  attn_row<T, VEC, NR, NT, true>(a, row, s, e, lane, tiles[wave], orow, srow);
+  attn_row<A, T, VEC, NR, NT, true>(a, row, s, e, lane, tiles[wave], keeps_of<A>(tiles[wave]), orow, srow);
 }
 
 // One wave per 128-entry chunk of a listed row: part[c, 0 .. D) unnormalised and pstat[c, h] = {m, l}, fp32.
-template <typename T, int VEC, int NR, int NT>
+template <class A, typename T, int VEC, int NR, int NT>
 __global__ void __launch_bounds__(kThreads)
-attn_half_fw_chunk_kernel(const FwArgs a, const unsigned long long* __restrict__ long_ctr,
+attn_half_fw_chunk_kernel(const A a, const unsigned long long* __restrict__ long_ctr,
                           const psa::LongEntry* __restrict__ long_list, float* __restrict__ part,
                           float* __restrict__ pstat) {
-  __shared__ float tiles[kWaves][64 * kHeadBlock];
+  __shared__ float tiles[kWaves][tile_floats<A>()];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const unsigned long long ctr = *long_ctr;
@@ -384,18 +422,20 @@ attn_half_fw_chunk_kernel(const FwArgs a, const unsigned long long* __restrict__
     clamp_range(rs, re, a.nnz);
     const int64_t s = rs + static_cast<int64_t>(c - ent.first_chunk) * psa::kLongChunk;
     const int64_t e = s + psa::kLongChunk < re ? s + psa::kLongChunk : re;
-    attn_row<T, VEC, NR, NT, false>(a, ent.row, s, e, lane, tiles[wave], part + static_cast<int64_t>(c) * D,
-                                    pstat + static_cast<int64_t>(c) * a.H * 2);
+    attn_row<A, T, VEC, NR, NT, false>(a, ent.row, s, e, lane, tiles[wave], keeps_of<A>(tiles[wave]),
+                                       part + static_cast<int64_t>(c) * D, pstat + static_cast<int64_t>(c) * a.H * 2);
   }
 }
 
 // One wave per listed row: its chunks' fp32 partials merged in chunk order, whatever order the list was built
 // in, then the one rounding.  An all -inf chunk carries {-inf, 0} and merges as nothing.
-template <typename T, int VEC>
+// DROP: inv_keep is applied here, once per output element and before the one rounding, not by the chunks.
+template <typename T, int VEC, bool DROP>
 __global__ void __launch_bounds__(kThreads)
 attn_half_fw_combine_kernel(int64_t H, int64_t F, const unsigned long long* __restrict__ long_ctr,
                             const psa::LongEntry* __restrict__ long_list, const float* __restrict__ part,
-                            const float* __restrict__ pstat, elem_t* __restrict__ out, float* __restrict__ stat) {
+                            const float* __restrict__ pstat, elem_t* __restrict__ out, float* __restrict__ stat,
+                            float inv_keep) {
   const int lane = threadIdx.x & 63;
   const int nrows = static_cast<int>(*long_ctr >> 32);
   const int num_waves = static_cast<int>(gridDim.x) * kWaves;
@@ -421,6 +461,10 @@ attn_half_fw_combine_kernel(int64_t H, int64_t F, const unsigned long long* __re
       }
 #pragma unroll
       for (int i = 0; i < VEC; ++i) acc[i] = acc[i] / l;
+      if constexpr (DROP) {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) acc[i] = __fmul_rn(acc[i], inv_keep);
+      }
       store_vec<T, VEC>(out + ent.row * D + d, acc);
       if (d % F == 0) {
         stat[(ent.row * H + h) * 2] = m;
@@ -450,11 +494,18 @@ struct BwArgs {
   DotGeo dotf;  // dP and delta: over F
   float* p;
   float* ds;
+  static constexpr bool kDrop = false;
 };
 
-// p and dS of the entries [s, e) of one row.
-template <typename T, int VEC, int NRK, int NRF>
-__device__ __forceinline__ void attn_bw_range(const BwArgs& a, int64_t row, int64_t s, int64_t e, int lane,
+struct BwDropArgs : BwArgs {
+  static constexpr bool kDrop = true;
+  psa::Drop drop;
+};
+
+// p and dS of the entries [s, e) of one row.  Dropout, with D = keep * inv_keep recomputed per (entry, head)
+// by the lane that writes it: p * D where p is written, and dS = p * (D * dP - delta).
+template <class A, typename T, int VEC, int NRK, int NRF>
+__device__ __forceinline__ void attn_bw_range(const A& a, int64_t row, int64_t s, int64_t e, int lane,
                                               float* __restrict__ tile_s, float* __restrict__ tile_p,
                                               float* __restrict__ delta) {
   const int bhstep = a.bias_heads == 1 ? 0 : 1;
@@ -483,17 +534,24 @@ __device__ __forceinline__ void attn_bw_range(const BwArgs& a, int64_t row, int6
         const float m = a.stat[(row * a.H + hb + h) * 2], l = a.stat[(row * a.H + hb + h) * 2 + 1];
         const float pe = expf(tile_s[idx * a.Hb + h] - m) / l;
         const int64_t at = (base + idx) * a.H + hb + h;
-        a.p[at] = pe;
-        a.ds[at] = pe * (tile_p[idx * a.Hb + h] - delta[h]);
+        if constexpr (A::kDrop) {
+          const bool kept = psa::keep_of(psa::rand_stream(a.drop.seed, base + idx), hb + h, a.drop.T);
+          const float dk = kept ? a.drop.inv_keep : 0.f;
+          a.p[at] = __fmul_rn(pe, dk);
+          a.ds[at] = pe * (__fmul_rn(dk, tile_p[idx * a.Hb + h]) - delta[h]);
+        } else {
+          a.p[at] = pe;
+          a.ds[at] = pe * (tile_p[idx * a.Hb + h] - delta[h]);
+        }
       }
       wave_sync();  // before the next tile overwrites
     }
   }
 }
 
-template <typename T, int VEC, int NRK, int NRF>
+template <class A, typename T, int VEC, int NRK, int NRF>
 __global__ void __launch_bounds__(kThreads)
-attn_half_bw_kernel(const BwArgs a, unsigned long long* __restrict__ long_ctr,
+attn_half_bw_kernel(const A a, unsigned long long* __restrict__ long_ctr,
                     psa::LongEntry* __restrict__ long_list) {
   __shared__ float tiles[kWaves][2][64 * kHeadBlock];
   __shared__ float deltas[kWaves][kHeadBlock];
@@ -508,13 +566,13 @@ attn_half_bw_kernel(const BwArgs a, unsigned long long* __restrict__ long_ctr,
     if (lane == 0) psa::push_long_row(long_ctr, long_list, row, e - s);
     return;
   }
-  attn_bw_range<T, VEC, NRK, NRF>(a, row, s, e, lane, tiles[wave][0], tiles[wave][1], deltas[wave]);
+  attn_bw_range<A, T, VEC, NRK, NRF>(a, row, s, e, lane, tiles[wave][0], tiles[wave][1], deltas[wave]);
 }
 
 // One wave per 128-entry chunk of a listed row; chunks write disjoint entries.
-template <typename T, int VEC, int NRK, int NRF>
+template <class A, typename T, int VEC, int NRK, int NRF>
 __global__ void __launch_bounds__(kThreads)
-attn_half_bw_chunk_kernel(const BwArgs a, const unsigned long long* __restrict__ long_ctr,
+attn_half_bw_chunk_kernel(const A a, const unsigned long long* __restrict__ long_ctr,
                           const psa::LongEntry* __restrict__ long_list) {
   __shared__ float tiles[kWaves][2][64 * kHeadBlock];
   __shared__ float deltas[kWaves][kHeadBlock];
@@ -530,7 +588,7 @@ attn_half_bw_chunk_kernel(const BwArgs a, const unsigned long long* __restrict__
     clamp_range(rs, re, a.nnz);
     const int64_t s = rs + static_cast<int64_t>(c - ent.first_chunk) * psa::kLongChunk;
     const int64_t e = s + psa::kLongChunk < re ? s + psa::kLongChunk : re;
-    attn_bw_range<T, VEC, NRK, NRF>(a, ent.row, s, e, lane, tiles[wave][0], tiles[wave][1], deltas[wave]);
+    attn_bw_range<A, T, VEC, NRK, NRF>(a, ent.row, s, e, lane, tiles[wave][0], tiles[wave][1], deltas[wave]);
   }
 }
 
@@ -586,31 +644,33 @@ int chunk_blocks(int64_t n) {
   return static_cast<int>(b > kMaxChunkBlocks ? kMaxChunkBlocks : b);
 }
 
-template <typename T, int VEC, int NR, int NT>
-int launch_fw(const FwArgs& a, elem_t* out, float* stat, unsigned long long* ctr, psa::LongEntry* list, float* part,
+template <class A, typename T, int VEC, int NR, int NT>
+int launch_fw(const A& a, elem_t* out, float* stat, unsigned long long* ctr, psa::LongEntry* list, float* part,
               float* pstat, hipStream_t s) {
   const int64_t gx = psa::ceil_div(a.M, kWaves);
   PSA_REQUIRE(gx <= 0x7fffffff, "M too large for one launch");
-  hipLaunchKernelGGL((attn_half_fw_kernel<T, VEC, NR, NT>), dim3(static_cast<unsigned>(gx)), dim3(kThreads), 0, s, a,
+  hipLaunchKernelGGL((attn_half_fw_kernel<A, T, VEC, NR, NT>), dim3(static_cast<unsigned>(gx)), dim3(kThreads), 0, s, a,
                      out, stat, ctr, list);
   if (list) {
-    hipLaunchKernelGGL((attn_half_fw_chunk_kernel<T, VEC, NR, NT>), dim3(chunk_blocks(psa::max_long_chunks(a.nnz))),
+    hipLaunchKernelGGL((attn_half_fw_chunk_kernel<A, T, VEC, NR, NT>), dim3(chunk_blocks(psa::max_long_chunks(a.nnz))),
                        dim3(kThreads), 0, s, a, ctr, list, part, pstat);
-    hipLaunchKernelGGL((attn_half_fw_combine_kernel<T, VEC>), dim3(chunk_blocks(psa::max_long_rows(a.nnz))),
-                       dim3(kThreads), 0, s, a.H, a.F, ctr, list, part, pstat, out, stat);
+    float inv_keep = 1.f;
+    if constexpr (A::kDrop) inv_keep = a.drop.inv_keep;
+    hipLaunchKernelGGL((attn_half_fw_combine_kernel<T, VEC, A::kDrop>), dim3(chunk_blocks(psa::max_long_rows(a.nnz))),
+                       dim3(kThreads), 0, s, a.H, a.F, ctr, list, part, pstat, out, stat, inv_keep);
   }
   PSA_LAUNCH_CHECK();
   return PSA_OK;
 }
 
-template <typename T, int VEC, int NRK, int NRF>
-int launch_bw(const BwArgs& a, unsigned long long* ctr, psa::LongEntry* list, hipStream_t s) {
+template <class A, typename T, int VEC, int NRK, int NRF>
+int launch_bw(const A& a, unsigned long long* ctr, psa::LongEntry* list, hipStream_t s) {
   const int64_t gx = psa::ceil_div(a.M, kWaves);
   PSA_REQUIRE(gx <= 0x7fffffff, "M too large for one launch");
-  hipLaunchKernelGGL((attn_half_bw_kernel<T, VEC, NRK, NRF>), dim3(static_cast<unsigned>(gx)), dim3(kThreads), 0, s,
+  hipLaunchKernelGGL((attn_half_bw_kernel<A, T, VEC, NRK, NRF>), dim3(static_cast<unsigned>(gx)), dim3(kThreads), 0, s,
                      a, ctr, list);
   if (list) {
-    hipLaunchKernelGGL((attn_half_bw_chunk_kernel<T, VEC, NRK, NRF>), dim3(chunk_blocks(psa::max_long_chunks(a.nnz))),
+    hipLaunchKernelGGL((attn_half_bw_chunk_kernel<A, T, VEC, NRK, NRF>), dim3(chunk_blocks(psa::max_long_chunks(a.nnz))),
                        dim3(kThreads), 0, s, a, ctr, list);
   }
   PSA_LAUNCH_CHECK();
@@ -619,31 +679,37 @@ int launch_bw(const BwArgs& a, unsigned long long* ctr, psa::LongEntry* list, hi
 
 inline const elem_t* elems(const void* p) { return static_cast<const elem_t*>(p); }
 
-}  // namespace
+// The entry points share their bodies with their dropout forms; errors carry the caller's name.
+#define ATTN_REQUIRE(cond, msg)                          \
+  do {                                                   \
+    if (!(cond)) {                                       \
+      psa::set_error(std::string(who) + ": " + (msg));   \
+      return PSA_ERR_INVALID_ARG;                        \
+    }                                                    \
+  } while (0)
 
-extern "C" {
-
-int psa_attention_half_fw(int dtype, const int64_t* rowptr, const int64_t* col, const void* q, const void* k,
-                          const void* v, const float* bias, int64_t bias_heads, float scale, int64_t M, int64_t N,
-                          int64_t H, int64_t K, int64_t F, int64_t nnz, void* out, float* stat, void* workspace,
-                          size_t workspace_bytes, psa_stream_t stream) {
-  PSA_REQUIRE(dtype == PSA_BF16, "dtype must be PSA_BF16");
-  PSA_REQUIRE(M >= 0 && N >= 0 && nnz >= 0, "negative size");
-  PSA_REQUIRE(H >= 1 && K >= 1 && F >= 1, "H, K and F must be at least 1");
-  PSA_REQUIRE(nnz < (int64_t{1} << 38), "nnz too large");
-  PSA_REQUIRE(H < (int64_t{1} << 24) && K < (int64_t{1} << 24) && F < (int64_t{1} << 24), "H, K or F too large");
-  PSA_REQUIRE(bias == nullptr || bias_heads == 1 || bias_heads == H, "bias_heads must be 1 or H");
+template <class A>
+int attention_fw(const char* who, const psa::Drop& drop, int dtype, const int64_t* rowptr, const int64_t* col,
+                 const void* q, const void* k, const void* v, const float* bias, int64_t bias_heads, float scale,
+                 int64_t M, int64_t N, int64_t H, int64_t K, int64_t F, int64_t nnz, void* out, float* stat,
+                 void* workspace, size_t workspace_bytes, psa_stream_t stream) {
+  ATTN_REQUIRE(dtype == PSA_BF16, "dtype must be PSA_BF16");
+  ATTN_REQUIRE(M >= 0 && N >= 0 && nnz >= 0, "negative size");
+  ATTN_REQUIRE(H >= 1 && K >= 1 && F >= 1, "H, K and F must be at least 1");
+  ATTN_REQUIRE(nnz < (int64_t{1} << 38), "nnz too large");
+  ATTN_REQUIRE(H < (int64_t{1} << 24) && K < (int64_t{1} << 24) && F < (int64_t{1} << 24), "H, K or F too large");
+  ATTN_REQUIRE(bias == nullptr || bias_heads == 1 || bias_heads == H, "bias_heads must be 1 or H");
   if (M == 0) return PSA_OK;
-  PSA_REQUIRE(rowptr && out && stat, "NULL pointer");
-  PSA_REQUIRE(nnz == 0 || (col && q && k && v), "NULL pointer");
-  PSA_REQUIRE(psa::aligned(q, 2) && psa::aligned(k, 2) && psa::aligned(v, 2) && psa::aligned(out, 2),
+  ATTN_REQUIRE(rowptr && out && stat, "NULL pointer");
+  ATTN_REQUIRE(nnz == 0 || (col && q && k && v), "NULL pointer");
+  ATTN_REQUIRE(psa::aligned(q, 2) && psa::aligned(k, 2) && psa::aligned(v, 2) && psa::aligned(out, 2),
               "operands must be 2-byte aligned");
   hipStream_t s = psa::as_stream(stream);
   unsigned long long* ctr = nullptr;
   psa::LongEntry* list = nullptr;
   float *part = nullptr, *pstat = nullptr;
   if (nnz > psa::kLongRow) {
-    const int rc = take_list("psa_attention_half_fw", workspace, workspace_bytes,
+    const int rc = take_list(who, workspace, workspace_bytes,
                              psa_attention_workspace_bytes(nnz, H, F), s, &ctr, &list);
     if (rc != PSA_OK) return rc;
     char* w = static_cast<char*>(workspace) + psa::long_list_bytes(nnz);
@@ -653,7 +719,8 @@ int psa_attention_half_fw(int dtype, const int64_t* rowptr, const int64_t* col, 
   const bool v8 = (K % 8 == 0) && (F % 8 == 0) && psa::aligned(q, 16) && psa::aligned(k, 16) && psa::aligned(v, 16) &&
                   psa::aligned(out, 16);
   const int vec = v8 ? 8 : 1;
-  FwArgs a;
+  A a;
+  if constexpr (A::kDrop) a.drop = drop;
   a.rowptr = rowptr;
   a.col = col;
   a.q = elems(q);
@@ -675,7 +742,7 @@ int psa_attention_half_fw(int dtype, const int64_t* rowptr, const int64_t* col, 
   a.ntiles = static_cast<int>(ntiles);
   const bool regs = a.dot.nit <= kMaxTiles;
   elem_t* o = static_cast<elem_t*>(out);
-#define PSA_ATTN_FW(VEC, NR, NT) return launch_fw<BF16, VEC, NR, NT>(a, o, stat, ctr, list, part, pstat, s)
+#define PSA_ATTN_FW(VEC, NR, NT) return launch_fw<A, BF16, VEC, NR, NT>(a, o, stat, ctr, list, part, pstat, s)
 #define PSA_ATTN_FW_NT(VEC, NR)         \
   do {                                  \
     if (ntiles == 1) PSA_ATTN_FW(VEC, NR, 1); \
@@ -696,34 +763,35 @@ int psa_attention_half_fw(int dtype, const int64_t* rowptr, const int64_t* col, 
 #undef PSA_ATTN_FW
 }
 
-int psa_attention_half_bw_entries(int dtype, const int64_t* rowptr, const int64_t* col, const void* q, const void* k,
-                                  const void* v, const float* bias, int64_t bias_heads, float scale,
-                                  const void* grad_out, const void* out, const float* stat, int64_t M, int64_t N,
-                                  int64_t H, int64_t K, int64_t F, int64_t nnz, float* p, float* ds, void* workspace,
-                                  size_t workspace_bytes, psa_stream_t stream) {
-  PSA_REQUIRE(dtype == PSA_BF16, "dtype must be PSA_BF16");
-  PSA_REQUIRE(M >= 0 && N >= 0 && nnz >= 0, "negative size");
-  PSA_REQUIRE(H >= 1 && K >= 1 && F >= 1, "H, K and F must be at least 1");
-  PSA_REQUIRE(nnz < (int64_t{1} << 38), "nnz too large");
-  PSA_REQUIRE(H < (int64_t{1} << 24) && K < (int64_t{1} << 24) && F < (int64_t{1} << 24), "H, K or F too large");
-  PSA_REQUIRE(bias == nullptr || bias_heads == 1 || bias_heads == H, "bias_heads must be 1 or H");
+template <class A>
+int attention_bw(const char* who, const psa::Drop& drop, int dtype, const int64_t* rowptr, const int64_t* col,
+                 const void* q, const void* k, const void* v, const float* bias, int64_t bias_heads, float scale,
+                 const void* grad_out, const void* out, const float* stat, int64_t M, int64_t N, int64_t H,
+                 int64_t K, int64_t F, int64_t nnz, float* p, float* ds, void* workspace, size_t workspace_bytes,
+                 psa_stream_t stream) {
+  ATTN_REQUIRE(dtype == PSA_BF16, "dtype must be PSA_BF16");
+  ATTN_REQUIRE(M >= 0 && N >= 0 && nnz >= 0, "negative size");
+  ATTN_REQUIRE(H >= 1 && K >= 1 && F >= 1, "H, K and F must be at least 1");
+  ATTN_REQUIRE(nnz < (int64_t{1} << 38), "nnz too large");
+  ATTN_REQUIRE(H < (int64_t{1} << 24) && K < (int64_t{1} << 24) && F < (int64_t{1} << 24), "H, K or F too large");
+  ATTN_REQUIRE(bias == nullptr || bias_heads == 1 || bias_heads == H, "bias_heads must be 1 or H");
   if (M == 0 || nnz == 0) return PSA_OK;
-  PSA_REQUIRE(rowptr && col && q && k && v && grad_out && out && stat && p && ds, "NULL pointer");
-  PSA_REQUIRE(psa::aligned(q, 2) && psa::aligned(k, 2) && psa::aligned(v, 2) && psa::aligned(grad_out, 2) &&
+  ATTN_REQUIRE(rowptr && col && q && k && v && grad_out && out && stat && p && ds, "NULL pointer");
+  ATTN_REQUIRE(psa::aligned(q, 2) && psa::aligned(k, 2) && psa::aligned(v, 2) && psa::aligned(grad_out, 2) &&
                   psa::aligned(out, 2),
               "operands must be 2-byte aligned");
   hipStream_t s = psa::as_stream(stream);
   unsigned long long* ctr = nullptr;
   psa::LongEntry* list = nullptr;
   if (nnz > psa::kLongRow) {
-    const int rc = take_list("psa_attention_half_bw_entries", workspace, workspace_bytes, psa::long_list_bytes(nnz), s,
-                             &ctr, &list);
+    const int rc = take_list(who, workspace, workspace_bytes, psa::long_list_bytes(nnz), s, &ctr, &list);
     if (rc != PSA_OK) return rc;
   }
   const bool v8 = (K % 8 == 0) && (F % 8 == 0) && psa::aligned(q, 16) && psa::aligned(k, 16) && psa::aligned(v, 16) &&
                   psa::aligned(grad_out, 16) && psa::aligned(out, 16);
   const int vec = v8 ? 8 : 1;
-  BwArgs a;
+  A a;
+  if constexpr (A::kDrop) a.drop = drop;
   a.rowptr = rowptr;
   a.col = col;
   a.q = elems(q);
@@ -746,7 +814,7 @@ int psa_attention_half_bw_entries(int dtype, const int64_t* rowptr, const int64_
   a.p = p;
   a.ds = ds;
   const bool rk = a.dot.nit <= kMaxTiles, rf = a.dotf.nit <= kMaxTiles;
-#define PSA_ATTN_BW(VEC, NRK, NRF) return launch_bw<BF16, VEC, NRK, NRF>(a, ctr, list, s)
+#define PSA_ATTN_BW(VEC, NRK, NRF) return launch_bw<A, BF16, VEC, NRK, NRF>(a, ctr, list, s)
 #define PSA_ATTN_BW_NR(VEC)           \
   do {                                \
     if (rk && rf) PSA_ATTN_BW(VEC, 4, 4); \
@@ -758,6 +826,54 @@ int psa_attention_half_bw_entries(int dtype, const int64_t* rowptr, const int64_
   PSA_ATTN_BW_NR(1);
 #undef PSA_ATTN_BW_NR
 #undef PSA_ATTN_BW
+}
+
+#undef ATTN_REQUIRE
+
+}  // namespace
+
+extern "C" {
+
+int psa_attention_half_fw(int dtype, const int64_t* rowptr, const int64_t* col, const void* q, const void* k,
+                          const void* v, const float* bias, int64_t bias_heads, float scale, int64_t M, int64_t N,
+                          int64_t H, int64_t K, int64_t F, int64_t nnz, void* out, float* stat, void* workspace,
+                          size_t workspace_bytes, psa_stream_t stream) {
+  return attention_fw<FwArgs>("psa_attention_half_fw", psa::Drop{}, dtype, rowptr, col, q, k, v, bias, bias_heads, scale,
+                              M, N, H, K, F, nnz, out, stat, workspace, workspace_bytes, stream);
+}
+
+int psa_attention_half_bw_entries(int dtype, const int64_t* rowptr, const int64_t* col, const void* q, const void* k,
+                                  const void* v, const float* bias, int64_t bias_heads, float scale,
+                                  const void* grad_out, const void* out, const float* stat, int64_t M, int64_t N,
+                                  int64_t H, int64_t K, int64_t F, int64_t nnz, float* p, float* ds, void* workspace,
+                                  size_t workspace_bytes, psa_stream_t stream) {
+  return attention_bw<BwArgs>("psa_attention_half_bw_entries", psa::Drop{}, dtype, rowptr, col, q, k, v, bias,
+                              bias_heads, scale, grad_out, out, stat, M, N, H, K, F, nnz, p, ds, workspace,
+                              workspace_bytes, stream);
+}
+
+int psa_attention_half_dropout_fw(int dtype, const int64_t* rowptr, const int64_t* col, const void* q, const void* k,
+                                  const void* v, const float* bias, int64_t bias_heads, float scale, double dropout_p,
+                                  uint64_t seed, int64_t M, int64_t N, int64_t H, int64_t K, int64_t F, int64_t nnz,
+                                  void* out, float* stat, void* workspace, size_t workspace_bytes,
+                                  psa_stream_t stream) {
+  psa::Drop drop;
+  if (!psa::make_drop("psa_attention_half_dropout_fw", dropout_p, seed, &drop)) return PSA_ERR_INVALID_ARG;
+  return attention_fw<FwDropArgs>("psa_attention_half_dropout_fw", drop, dtype, rowptr, col, q, k, v, bias, bias_heads,
+                                  scale, M, N, H, K, F, nnz, out, stat, workspace, workspace_bytes, stream);
+}
+
+int psa_attention_half_dropout_bw_entries(int dtype, const int64_t* rowptr, const int64_t* col, const void* q,
+                                          const void* k, const void* v, const float* bias, int64_t bias_heads,
+                                          float scale, double dropout_p, uint64_t seed, const void* grad_out,
+                                          const void* out, const float* stat, int64_t M, int64_t N, int64_t H,
+                                          int64_t K, int64_t F, int64_t nnz, float* p, float* ds, void* workspace,
+                                          size_t workspace_bytes, psa_stream_t stream) {
+  psa::Drop drop;
+  if (!psa::make_drop("psa_attention_half_dropout_bw_entries", dropout_p, seed, &drop)) return PSA_ERR_INVALID_ARG;
+  return attention_bw<BwDropArgs>("psa_attention_half_dropout_bw_entries", drop, dtype, rowptr, col, q, k, v, bias,
+                                  bias_heads, scale, grad_out, out, stat, M, N, H, K, F, nnz, p, ds, workspace,
+                                  workspace_bytes, stream);
 }
 
 }  // extern "C"

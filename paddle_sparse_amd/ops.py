@@ -1875,8 +1875,45 @@ def _bias_heads(bias: Optional[torch.Tensor]) -> int:
     return 1 if bias is None or bias.dim() == 1 else bias.shape[1]
 
 
-def _attention_fw_raw(rowptr, col, q, k, v, bias, scale: float):
-    """(out [M, H, F], stat [M, H, 2] = {row maximum, sum of exp(s - maximum)}) from checked heads-form operands."""
+def _dropout_args(dropout_p, seed, who: str = "attention", draw: bool = True):
+    """(dropout_p, seed) checked: a float in [0, 1) and an int in [0, 2^64).  seed=None with dropout_p > 0 draws one
+    from torch's CPU default generator where `draw` allows it (torch.manual_seed reproduces it; no device read, no
+    sync).  With dropout_p == 0 the seed is not looked at and comes back as 0."""
+    if isinstance(dropout_p, bool) or not isinstance(dropout_p, (int, float)):
+        raise ValueError(f"{who}: dropout_p must be a float in [0, 1) (got {dropout_p!r})")
+    dropout_p = float(dropout_p)
+    if not 0.0 <= dropout_p < 1.0:  # a NaN fails both comparisons
+        raise ValueError(f"{who}: dropout_p must be in [0, 1) (got {dropout_p})")
+    if dropout_p == 0.0:
+        return 0.0, 0
+    if seed is None and draw:
+        lo, hi = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
+        return dropout_p, (hi << 32) | lo
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise TypeError(f"{who}: seed must be an int in [0, 2^64) (got {type(seed).__name__})")
+    if not 0 <= seed < (1 << 64):
+        raise ValueError(f"{who}: seed must be in [0, 2^64) (got {seed})")
+    return dropout_p, seed
+
+
+def attention_dropout_mask(nnz: int, H: int, dropout_p: float, seed: int, device="cuda") -> torch.Tensor:
+    """bool [nnz, H] on the device: keep(e, h) of the fused op's dropout for this (dropout_p, seed), e the position
+    of the entry in CSR order and h the head (psa_attention_dropout_mask).  The unfused chain with the same mask is
+    spmm_heads(softmax(sddmm) * mask * float32(1 / (1 - dropout_p)), v)."""
+    if isinstance(nnz, bool) or isinstance(H, bool) or not isinstance(nnz, int) or not isinstance(H, int):
+        raise TypeError("attention_dropout_mask: nnz and H must be ints")
+    if nnz < 0 or H < 1:
+        raise ValueError("attention_dropout_mask: nnz must be at least 0 and H at least 1")
+    p, seed = _dropout_args(dropout_p, seed, "attention_dropout_mask", draw=False)
+    mask = torch.empty((nnz, H), dtype=torch.uint8, device=device)
+    with _on(mask.device):
+        check(_lib.load().psa_attention_dropout_mask(nnz, H, p, seed, _ptr(mask), _stream()))
+    return mask.view(torch.bool)
+
+
+def _attention_fw_raw(rowptr, col, q, k, v, bias, scale: float, dropout_p: float = 0.0, seed: int = 0):
+    """(out [M, H, F], stat [M, H, 2] = {row maximum, sum of exp(s - maximum)}) from checked heads-form operands;
+    dropout_p == 0.0 takes the plain entry points, anything else the dropout forms (with a checked seed)."""
     M, H, K = q.shape
     N, F, nnz = k.shape[0], v.shape[2], col.numel()
     out = torch.empty((M, H, F), dtype=q.dtype, device=q.device)
@@ -1885,7 +1922,15 @@ def _attention_fw_raw(rowptr, col, q, k, v, bias, scale: float):
     ws_bytes = lib.psa_attention_workspace_bytes(nnz, H, F)  # the partials are fp32 for either dtype
     ws = _workspace(ws_bytes, q.device) if ws_bytes else None
     with _on(q.device):
-        if q.dtype == torch.float32:
+        if dropout_p != 0.0 and q.dtype == torch.float32:
+            check(lib.psa_attention_dropout_fw(_ptr(rowptr), _ptr(col), _ptr(q), _ptr(k), _ptr(v), _ptr(bias),
+                                               _bias_heads(bias), scale, dropout_p, seed, M, N, H, K, F, nnz, _ptr(out),
+                                               _ptr(stat), _ptr(ws), ws_bytes, _stream()))
+        elif dropout_p != 0.0:
+            check(lib.psa_attention_half_dropout_fw(_DTYPE_ID[q.dtype], _ptr(rowptr), _ptr(col), _ptr(q), _ptr(k),
+                                                    _ptr(v), _ptr(bias), _bias_heads(bias), scale, dropout_p, seed, M, N,
+                                                    H, K, F, nnz, _ptr(out), _ptr(stat), _ptr(ws), ws_bytes, _stream()))
+        elif q.dtype == torch.float32:
             check(lib.psa_attention_fw(_ptr(rowptr), _ptr(col), _ptr(q), _ptr(k), _ptr(v), _ptr(bias),
                                        _bias_heads(bias), scale, M, N, H, K, F, nnz, _ptr(out), _ptr(stat), _ptr(ws),
                                        ws_bytes, _stream()))
@@ -1896,8 +1941,10 @@ def _attention_fw_raw(rowptr, col, q, k, v, bias, scale: float):
     return out, stat
 
 
-def _attention_bw_entries_raw(rowptr, col, q, k, v, bias, scale: float, grad_out, out, stat):
-    """(p [nnz, H], dS = p * (dP - delta) [nnz, H]): the per-entry half of the backward, from the saved {m, l}."""
+def _attention_bw_entries_raw(rowptr, col, q, k, v, bias, scale: float, grad_out, out, stat, dropout_p: float = 0.0,
+                              seed: int = 0):
+    """(p [nnz, H], dS = p * (dP - delta) [nnz, H]): the per-entry half of the backward, from the saved {m, l}.
+    With dropout (D = keep * inv_keep, recomputed from the seed): (p * D, p * (D * dP - delta))."""
     M, H, K = q.shape
     N, F, nnz = k.shape[0], v.shape[2], col.numel()
     if grad_out.dtype != q.dtype:
@@ -1910,7 +1957,18 @@ def _attention_bw_entries_raw(rowptr, col, q, k, v, bias, scale: float, grad_out
     ws_bytes = lib.psa_attention_workspace_bytes(nnz, H, F)
     ws = _workspace(ws_bytes, q.device) if ws_bytes else None
     with _on(q.device):
-        if q.dtype == torch.float32:
+        if dropout_p != 0.0 and q.dtype == torch.float32:
+            check(lib.psa_attention_dropout_bw_entries(_ptr(rowptr), _ptr(col), _ptr(q), _ptr(k), _ptr(v), _ptr(bias),
+                                                       _bias_heads(bias), scale, dropout_p, seed, _ptr(grad_out),
+                                                       _ptr(out), _ptr(stat), M, N, H, K, F, nnz, _ptr(p), _ptr(ds),
+                                                       _ptr(ws), ws_bytes, _stream()))
+        elif dropout_p != 0.0:
+            check(lib.psa_attention_half_dropout_bw_entries(_DTYPE_ID[q.dtype], _ptr(rowptr), _ptr(col), _ptr(q),
+                                                            _ptr(k), _ptr(v), _ptr(bias), _bias_heads(bias), scale,
+                                                            dropout_p, seed, _ptr(grad_out), _ptr(out), _ptr(stat), M, N,
+                                                            H, K, F, nnz, _ptr(p), _ptr(ds), _ptr(ws), ws_bytes,
+                                                            _stream()))
+        elif q.dtype == torch.float32:
             check(lib.psa_attention_bw_entries(_ptr(rowptr), _ptr(col), _ptr(q), _ptr(k), _ptr(v), _ptr(bias),
                                                _bias_heads(bias), scale, _ptr(grad_out), _ptr(out), _ptr(stat), M, N, H,
                                                K, F, nnz, _ptr(p), _ptr(ds), _ptr(ws), ws_bytes, _stream()))
@@ -1922,21 +1980,25 @@ def _attention_bw_entries_raw(rowptr, col, q, k, v, bias, scale: float, grad_out
     return p, ds
 
 
-def attention_raw(rowptr, col, q, k, v, bias=None, scale: float = 1.0):
-    """The forward alone, without autograd: (out, stat) with stat [M, H, 2] = {m, l} (2-D operands: [M, 2])."""
+def attention_raw(rowptr, col, q, k, v, bias=None, scale: float = 1.0, dropout_p: float = 0.0, seed: int = 0):
+    """The forward alone, without autograd: (out, stat) with stat [M, H, 2] = {m, l} (2-D operands: [M, 2]).
+    dropout_p > 0 takes the dropout entry points with this seed (an int: attention_bw needs the same one)."""
     rowptr, col, q, k, v, bias, _, flat = _attention_operands(rowptr, col, q, k, v, bias)
+    dropout_p, seed = _dropout_args(dropout_p, seed, draw=False)
     out, stat = _attention_fw_raw(rowptr, col, q.detach(), k.detach(), v.detach(),
-                                  None if bias is None else bias.detach(), float(scale))
+                                  None if bias is None else bias.detach(), float(scale), dropout_p, seed)
     return (out[:, 0], stat[:, 0]) if flat else (out, stat)
 
 
 def attention_bw(rowptr, col, q, k, v, bias, scale: float, grad_out, out, stat, csc=None,
-                 want=(True, True, True, True)):
+                 want=(True, True, True, True), dropout_p: float = 0.0, seed: int = 0):
     """(grad_q, grad_k, grad_v, grad_bias) of attention from what its forward left (heads-form operands, out and
-    stat of attention_raw); None where `want` says so.  p and dS [nnz, H] live only inside this call."""
+    stat of attention_raw); None where `want` says so.  p and dS [nnz, H] live only inside this call.  dropout_p and
+    seed are the forward's: the mask is recomputed from them, and p below is then p * keep * inv_keep."""
     want_q, want_k, want_v, want_b = want
     grad_out = grad_out.contiguous()
-    p, ds = _attention_bw_entries_raw(rowptr, col, q, k, v, bias, scale, grad_out, out, stat)
+    dropout_p, seed = _dropout_args(dropout_p, seed, draw=False)
+    p, ds = _attention_bw_entries_raw(rowptr, col, q, k, v, bias, scale, grad_out, out, stat, dropout_p, seed)
     grad_q = grad_k = grad_v = grad_b = None
     if q.dtype != torch.float32:  # psa_spmm_heads_half: fp32 sums, scale before the one rounding, no fp32 copies
         if want_q:
@@ -1972,10 +2034,11 @@ class _Attention(torch.autograd.Function):
     rows of its own (the pattern is the caller's and rides on ctx)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, bias, rowptr, col, scale, csc):
-        out, stat = _attention_fw_raw(rowptr, col, q, k, v, bias, scale)
+    def forward(ctx, q, k, v, bias, rowptr, col, scale, csc, dropout_p, seed):
+        out, stat = _attention_fw_raw(rowptr, col, q, k, v, bias, scale, dropout_p, seed)
         ctx.save_for_backward(q, k, v, bias, out, stat)
         ctx.pattern, ctx.scale, ctx.csc = (rowptr, col), scale, csc
+        ctx.dropout_p, ctx.seed = dropout_p, seed  # two Python scalars: the backward recomputes the mask
         return out
 
     @staticmethod
@@ -1983,12 +2046,13 @@ class _Attention(torch.autograd.Function):
         q, k, v, bias, out, stat = ctx.saved_tensors
         rowptr, col = ctx.pattern
         grads = attention_bw(rowptr, col, q, k, v, bias, ctx.scale, grad, out, stat, ctx.csc,
-                             ctx.needs_input_grad[:4])
-        return grads + (None, None, None, None)
+                             ctx.needs_input_grad[:4], ctx.dropout_p, ctx.seed)
+        return grads + (None, None, None, None, None, None)
 
 
 def attention(rowptr: torch.Tensor, col: torch.Tensor, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
-              bias: Optional[torch.Tensor] = None, scale: float = 1.0, csc=None) -> torch.Tensor:
+              bias: Optional[torch.Tensor] = None, scale: float = 1.0, csc=None, dropout_p: float = 0.0,
+              seed: Optional[int] = None) -> torch.Tensor:
     """[M, H, F]: out[r, h, :] = sum over the entries of row r of p[e, h] * v[col[e], h, :], p[., h] the softmax
     over the row of s[e, h] = scale * <q[row(e), h, :], k[col[e], h, :]> (+ bias[e, h] or bias[e]), with q
     [M, H, K], k [N, H, K], v [N, H, F] all float32 or all bfloat16 and bias fp32 [nnz] or [nnz, H]; 2-D q, k, v
@@ -1997,11 +2061,21 @@ def attention(rowptr: torch.Tensor, col: torch.Tensor, q: torch.Tensor, k: torch
     from psa_spmm_heads over the CSR and the CSC view.  bfloat16 operands (psa_attention_half_fw /
     _bw_entries / psa_spmm_heads_half) give a bfloat16 out and bfloat16 gradients: gathers are half-width,
     all arithmetic, stat and grad_bias are fp32, each bfloat16 result is rounded once.  Differentiable in
-    q, k, v and bias; `scale` is a float.  `csc` as for sddmm."""
+    q, k, v and bias; `scale` is a float.  `csc` as for sddmm.
+
+    dropout_p in [0, 1) drops attention weights after the softmax, inside the kernels (the psa_attention_*dropout*
+    entry points): out = inv_keep * sum keep(e, h) * p[e, h] * v[col[e], h, :] with inv_keep = float32(1 / (1 -
+    dropout_p)) and keep(e, h) a counter-based draw that depends on (seed, position of the entry in CSR order, head)
+    only, so fp32 and bf16 operands drop the same entries and attention_dropout_mask(nnz, H, dropout_p, seed) gives
+    the same mask to the unfused chain.  The backward recomputes the mask; nothing more is saved.  `seed` is an int
+    in [0, 2^64); seed=None draws one from torch's CPU default generator (torch.manual_seed reproduces a run; no
+    device read, no sync).  The seed is a launch argument: a captured graph replays the same mask at every replay.
+    dropout_p == 0.0 is the op without dropout, bit for bit, and ignores the seed."""
     rowptr, col, q, k, v, bias, _, flat = _attention_operands(rowptr, col, q, k, v, bias)
     scale = float(scale)
+    dropout_p, seed = _dropout_args(dropout_p, seed)  # resolved here: forward and backward see one value
     if needs_grad(q) or needs_grad(k) or needs_grad(v) or needs_grad(bias):
-        out = _Attention.apply(q, k, v, bias, rowptr, col, scale, csc)
+        out = _Attention.apply(q, k, v, bias, rowptr, col, scale, csc, dropout_p, seed)
     else:
-        out = _attention_fw_raw(rowptr, col, q, k, v, bias, scale)[0]
+        out = _attention_fw_raw(rowptr, col, q, k, v, bias, scale, dropout_p, seed)[0]
     return out[:, 0] if flat else out

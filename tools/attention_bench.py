@@ -34,10 +34,17 @@ forward + backward, each with its [min .. max]: a difference counts only where i
 of DESIGN.md section 3.11 for the bf16 forward: reads nnz*(8 + 2HK + 2HF), writes M*(2HF + 8H).  Under each pair
 the peak memory of one forward + backward of each side.
 
-usage: python tools/attention_bench.py [--quick] [--once] [--heads] [--fused [--dtype bf16]]
+With --dropout P the fused lines run SparseTensor.attention(..., dropout_p=P) beside the same op without dropout
+and beside the chain with a materialised mask, (att * mask * inv_keep) @ v with the mask of
+ops.attention_dropout_mask, alternating call by call, and print the peak memory of one forward + backward of each;
+with --dtype bf16 the two fused sides take bfloat16 operands (the chain stays fp32).  Dropout moves no extra bytes
+(the mask is recomputed), so the byte model is that of the op without it.
+
+usage: python tools/attention_bench.py [--quick] [--once] [--heads] [--fused [--dtype bf16] [--dropout P]]
   --quick  config 3 only;  --once  one call of each of our ops and nothing else (for a kernel trace);
   --heads  the multi-head lines only;  --fused  the fused-attention lines only;
-  --dtype bf16  (with --fused) the bf16 fused op beside the fp32 fused op"""
+  --dtype bf16  (with --fused) the bf16 fused op beside the fp32 fused op
+  --dropout P   (with --fused) the fused op with dropout beside the op without and the chain with the same mask"""
 import statistics
 import sys
 from pathlib import Path
@@ -299,6 +306,65 @@ def run_fused_bf16(N, rowptr, col, gen, once):
         torch.cuda.empty_cache()
 
 
+def run_fused_dropout(N, rowptr, col, gen, once, drop, half):
+    """The fused op with dropout ("ours" of each line) beside the fused op without it and beside the chain with a
+    materialised mask, (att * mask * inv_keep) @ v, the mask from ops.attention_dropout_mask under the same seed.
+    The chain is fp32; with --dtype bf16 it is fed the fp32 copies of the same values."""
+    nnz = col.numel()
+    A = SparseTensor(rowptr=rowptr, col=col, sparse_sizes=(N, N), is_sorted=True, trust_data=True)
+    A.storage.csr2csc()  # the CSC view of the backward, built once as a training loop has it
+    seed, inv_keep = 12345, float(torch.tensor(1.0 / (1.0 - drop), dtype=torch.float32))
+    dt = torch.bfloat16 if half else torch.float32
+    for H, K in ((8, 16), (8, 64), (1, 64)):
+        F = K
+        dense, edge = N * H * K * 4, nnz * H * 4
+        tag = f"H = {H}, K = F = {K}, dropout {drop}"
+        if not fits((12 if half else 8) * dense + 2 * edge):
+            print(f"   {tag}: not run, the operands and gradients alone do not fit", flush=True)
+            continue
+        chain_fits = fits((12 if half else 8) * dense + 10 * edge)  # as --fused, plus the mask and the masked weights
+        q, k, v, go = (t.to(dt) for t in (
+            torch.randn((N, H, K), generator=gen, device=dev) * 0.125, torch.randn((N, H, K), generator=gen, device=dev),
+            torch.randn((N, H, F), generator=gen, device=dev), torch.randn((N, H, F), generator=gen, device=dev)))
+        q32, k32, v32, go32 = ((t.float() for t in (q, k, v, go)) if half else (q, k, v, go))
+
+        def forward(kind, qq=None, kk=None, vv=None):
+            if kind == "chain":
+                qq, kk, vv = (q32, k32, v32) if qq is None else (qq, kk, vv)
+                mask = ops.attention_dropout_mask(nnz, H, drop, seed)
+                att = psa.sddmm(A, qq, kk).softmax(dim=1)
+                return att.set_value(att.storage.value() * mask * inv_keep, layout="coo") @ vv
+            qq, kk, vv = (q, k, v) if qq is None else (qq, kk, vv)
+            return A.attention(qq, kk, vv, dropout_p=drop if kind == "dropout" else 0.0, seed=seed)
+
+        def step(kind):
+            def run():
+                src = (q32, k32, v32) if kind == "chain" else (q, k, v)
+                qq, kk, vv = (t.detach().requires_grad_() for t in src)
+                forward(kind, qq, kk, vv).backward(go32 if kind == "chain" else go)
+            return run
+
+        step("dropout")()
+        if once:
+            continue
+        if chain_fits:
+            diff = float((forward("dropout").float() - forward("chain")).abs().max())
+            print(f"   {tag}: max |fused - chain with the same mask| = {diff:.2e}", flush=True)
+        width = 2 if half else 4
+        model = nnz * (8 + width * H * K + width * H * F) + N * (width * H * F + 8 * H)  # dropout moves no extra bytes
+        heads_line(f"attention forward, {tag}",
+                   [("dropout", lambda: forward("dropout")), ("plain", lambda: forward("plain")),
+                    ("masked chain", (lambda: forward("chain")) if chain_fits else None)], model)
+        heads_line(f"attention fwd + bwd, {tag}",
+                   [("dropout", step("dropout")), ("plain", step("plain")),
+                    ("masked chain", step("chain") if chain_fits else None)])
+        peak_c = f"{peak_of(step('chain')):7.3f} GB" if chain_fits else "not run (memory)"
+        print(f"   {'peak memory of one fwd + bwd':34s} dropout {peak_of(step('dropout')):7.3f} GB   "
+              f"plain {peak_of(step('plain')):7.3f} GB   masked chain {peak_c}", flush=True)
+        del q, k, v, go, q32, k32, v32, go32
+        torch.cuda.empty_cache()
+
+
 def torch_softmax(v, row, M):
     shape = (M,) + tuple(v.shape[1:])
     m = torch.zeros(shape, device=dev).scatter_reduce(0, row.view((-1,) + (1,) * (v.dim() - 1)).expand_as(v), v, "amax",
@@ -333,7 +399,7 @@ def rmat24():
     return N, rowptr, col
 
 
-def run(name, make, once, heads_only=False, fused_only=False, half=False):
+def run(name, make, once, heads_only=False, fused_only=False, half=False, drop=None):
     N, rowptr, col = make()
     nnz = col.numel()
     row = ops.ptr2ind(rowptr, nnz)
@@ -343,7 +409,10 @@ def run(name, make, once, heads_only=False, fused_only=False, half=False):
     gen = torch.Generator(device=dev).manual_seed(9)
     if fused_only:
         del row
-        (run_fused_bf16 if half else run_fused)(N, rowptr, col, gen, once)
+        if drop is not None:
+            run_fused_dropout(N, rowptr, col, gen, once, drop, half)
+        else:
+            (run_fused_bf16 if half else run_fused)(N, rowptr, col, gen, once)
         return
     if heads_only:
         run_heads(N, rowptr, col, row, gen, once)
@@ -417,6 +486,15 @@ if __name__ == "__main__":
         if dtype not in (["bf16"], ["fp32"]) or not fused_only:
             sys.exit("--dtype takes bf16 or fp32 and goes with --fused")
         half = dtype == ["bf16"]
-    run("config-3 shape", config3, once, heads_only, fused_only, half)
+    drop = None
+    if "--dropout" in sys.argv:
+        arg = sys.argv[sys.argv.index("--dropout") + 1:][:1]
+        try:
+            drop = float(arg[0])
+        except (IndexError, ValueError):
+            drop = -1.0
+        if not 0.0 < drop < 1.0 or not fused_only:
+            sys.exit("--dropout takes a probability in (0, 1) and goes with --fused")
+    run("config-3 shape", config3, once, heads_only, fused_only, half, drop)
     if "--quick" not in sys.argv:
-        run("R-MAT 24", rmat24, once, heads_only, fused_only, half)
+        run("R-MAT 24", rmat24, once, heads_only, fused_only, half, drop)
