@@ -11,6 +11,7 @@ from __future__ import annotations
 import torch
 
 from . import elementwise as ew
+from . import ops
 from .coalesce import _ONE_WORKGROUP_BELOW, _coalesce_sorted_stream, _coalesce_two_sorted
 from .tensor import SparseTensor
 
@@ -24,6 +25,7 @@ def _add_sparse(a: SparseTensor, b: SparseTensor) -> SparseTensor:
     """Union of the stored entries, values of shared entries added.  The result
     has values only when both operands do (add.py:37-39)."""
     shape = (max(a.size(0), b.size(0)), max(a.size(1), b.size(1)))
+    ops.key_bound(shape[0], shape[1], "add")
     (ra, ca, va), (rb, cb, vb) = a.coo(), b.coo()
     if ra.numel() + rb.numel() > _ONE_WORKGROUP_BELOW:
         # both operands are in (row, col) order: merge, don't sort

@@ -25,6 +25,7 @@ _CHAIN_BELOW = 1 << 20  # entries: the two-call chain (always sorts); above, ask
 
 
 def _coalesce_sorted_stream(row, col, value, m: int, n: int, op: str):
+    ops.key_bound(m, n, "coalesce")
     nnz = col.numel()
     if nnz == 0:
         return row, col, value
@@ -114,6 +115,7 @@ def coalesce(index: torch.Tensor, value: Optional[torch.Tensor], m: int, n: int,
              op: str = "add") -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Row-wise sorts `index` and merges duplicate entries with `op`
     ("add"/"sum", "mean", "min", "max").  Returns (index[2, nnz'], value)."""
+    ops.key_bound(m, n, "coalesce")
     row, col = index[0].contiguous(), index[1].contiguous()
     assert row.dtype == torch.int64 and col.dtype == torch.int64
     nnz = col.numel()

@@ -21,6 +21,7 @@ mul_nnz_ = ew.nnz_variant("mul", inplace=True)
 
 
 def _mul_sparse(a: SparseTensor, b: SparseTensor) -> SparseTensor:
+    ops.key_bound(max(a.size(0), b.size(0)), max(a.size(1), b.size(1)), "mul")
     for name, t in (("src", a), ("other", b)):
         if not t.is_coalesced():
             raise ValueError(f"The `{name}` tensor is not coalesced")

@@ -496,6 +496,7 @@ def coalesce_small(row: torch.Tensor, col: torch.Tensor, m: int, n: int):
     (inputs of at most coalesce_small_max() entries; see the header).  Returns
     (count, ptr int64[count + 1], row' int64[count], col' int64[count], perm
     int64[nnz]) like index_sort + unique_sorted.  One host read (count)."""
+    key_bound(m, n, "coalesce_small")
     row, col = _index(row, "row"), _index(col, "col")
     nnz = row.numel()
     dev = row.device
@@ -518,6 +519,18 @@ class IndexRangeError(AssertionError):
     row.max() < M and col.max() < N, storage.py:78-91)."""
 
 
+def key_bound(rows: int, cols: int, who: str) -> int:
+    """rows * cols: the exclusive bound of the keys row * cols + col of a rows x cols matrix, as the sorts take it.
+    ValueError when it does not fit a signed 64-bit integer: the keys would wrap, and ctypes would hand the C entry
+    points a wrapped bound without a word.  Host arithmetic only; every op that forms such keys asks before its
+    first launch."""
+    rows, cols = int(rows), int(cols)
+    if rows * cols >= (1 << 63):
+        raise ValueError(f"{who}: the keys row * {cols} + col of a {rows} x {cols} matrix do not fit 63 bits "
+                         f"({rows} * {cols} >= 2^63)")
+    return rows * cols
+
+
 _FUSED_SMALL = 10_240  # entries the one-launch coalesce takes (psa_coalesce_small_max_fused)
 
 
@@ -535,6 +548,7 @@ def coalesce_chain(row: torch.Tensor, col: torch.Tensor, value: Optional[torch.T
     (index int64[2, count] contiguous, value' | None, was_sorted).  With
     read_first the count is read between the calls and the outputs are sized
     exactly; otherwise both calls are enqueued on worst-case buffers first."""
+    key_bound(m, n, "coalesce")
     row, col = _index(row, "row"), _index(col, "col")
     nnz, dev = row.numel(), row.device
     if col.numel() != nnz:
@@ -594,6 +608,7 @@ def coalesce_chain(row: torch.Tensor, col: torch.Tensor, value: Optional[torch.T
 def make_keys_checked(row: torch.Tensor, col: torch.Tensor, m: int, n: int):
     """keys = row * n + col plus the device status words {0, flags}: bit 0 = an
     index outside [0, m) x [0, n), bit 1 = keys not sorted (storage.py:159-163)."""
+    key_bound(m, n, "make_keys_checked")
     row, col = _index(row, "row"), _index(col, "col")
     keys = torch.empty_like(row)
     status = torch.empty(4, dtype=torch.int64, device=row.device)

@@ -35,6 +35,8 @@ def _ragged_take(old_ptr: torch.Tensor, counts: torch.Tensor, idx: torch.Tensor)
 def index_select(src: SparseTensor, dim: int, idx: torch.Tensor) -> SparseTensor:
     dim = src.dim() + dim if dim < 0 else dim
     assert idx.dim() == 1
+    if dim == 1:  # the keys row * idx.numel() + col of the re-sort below; asked before idx is even copied
+        ops.key_bound(src.sparse_size(0), max(idx.numel(), 1), "index_select")
     idx = idx.to(torch.int64).contiguous()
     if dim == 0:  # index_select.py:17-49
         old_rowptr, col, value = src.csr()
@@ -49,7 +51,8 @@ def index_select(src: SparseTensor, dim: int, idx: torch.Tensor) -> SparseTensor
         colcount, colptr, col, perm = _ragged_take(old_colptr, src.storage.colcount(), idx)
         row = ops.gather_rows(row, perm)
         keys, _ = ops.make_keys(row, col, idx.numel())
-        _, csc2csr = ops.index_sort(keys, src.sparse_size(0) * max(idx.numel(), 1), check=True)
+        _, csc2csr = ops.index_sort(keys, ops.key_bound(src.sparse_size(0), max(idx.numel(), 1), "index_select"),
+                                    check=True)
         if value is not None:
             value = ops.gather_rows(ops.gather_rows(value, perm), csc2csr)
         storage = SparseStorage(row=ops.gather_rows(row, csc2csr), col=ops.gather_rows(col, csc2csr),

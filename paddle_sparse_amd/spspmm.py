@@ -40,6 +40,7 @@ from .coalesce import _stack_index, coalesce
 
 def _spspmm_csr(rowA, colA, valueA, rowptrB, colB, valueB, m: int, n: int):
     """A as sorted COO (row, col, value), B as CSR; returns (row, col, value) of C."""
+    ops.key_bound(m, n, "spspmm")  # the keys i * n + j
     dtype = valueA.dtype if valueA is not None else (valueB.dtype if valueB is not None else torch.float32)
     device = colA.device
     empty_i = torch.empty(0, dtype=torch.int64, device=device)
@@ -158,6 +159,7 @@ def spspmm(indexA: torch.Tensor, valueA: Optional[torch.Tensor], indexB: torch.T
     Both must be coalesced (row-major sorted, no duplicates); `coalesced=True`
     coalesces them first.  Returns the coalesced (index, value) of the [m, n]
     product.  The values are differentiable in valueA and valueB."""
+    ops.key_bound(m, n, "spspmm")  # before the first launch
     if coalesced:
         indexA, valueA = coalesce(indexA, valueA, m, k)
         indexB, valueB = coalesce(indexB, valueB, k, n)

@@ -128,6 +128,7 @@ class SparseStorage(object):
 
         # storage.py:158-171 — sort by (row, col) unless told it is sorted
         if not is_sorted and nnz > 0:
+            ops.key_bound(M, N, "SparseStorage")
             keys, unsorted = ops.make_keys(self.row(), self._col, N, check_sorted=True)
             if int(unsorted.item()):
                 # row[perm] / col[perm] (storage.py:166-167) are read back
@@ -510,6 +511,7 @@ class SparseStorage(object):
         nnz = self._col.numel()
         if nnz == 0:
             return True
+        ops.key_bound(*self._sparse_sizes, "is_coalesced")
         keys, unsorted = ops.make_keys(self.row(), self._col, self._sparse_sizes[1], check_sorted=True)
         count, _, _, _ = ops.unique_sorted(keys, 1, want_ptr=False, want_rowcol=False)
         return count == nnz and not int(unsorted.item())
@@ -520,6 +522,7 @@ class SparseStorage(object):
         if nnz == 0:
             return self
         N = self._sparse_sizes[1]
+        ops.key_bound(self._sparse_sizes[0], N, "coalesce")
         keys, _ = ops.make_keys(self.row(), self._col, N)
         value = self._value
         if (value is not None and value.dim() == 1 and value.dtype in (torch.float32, torch.int32)

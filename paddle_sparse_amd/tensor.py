@@ -252,6 +252,7 @@ class SparseTensor(object):
         """tensor.py:415-451: union of A and A^T, duplicates reduced.  Built on
         the same sort + run-length + segmented-reduce kernels as coalesce()."""
         N = max(self.size(0), self.size(1))
+        ops.key_bound(N, N, "to_symmetric")
         row, col, value = self.coo()
         n = row.numel()
         if 2 * n > _MERGE_ABOVE:
