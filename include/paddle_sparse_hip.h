@@ -1054,6 +1054,63 @@ int psa_attention_half_dropout_bw_entries(int dtype, const int64_t* rowptr, cons
 int psa_attention_dropout_mask(int64_t nnz, int64_t H, double dropout_p, uint64_t seed, uint8_t* mask,
                                psa_stream_t stream);
 
+/* ---- fused GAT attention: the additive scores of a graph attention layer through the one-pass
+ * kernels above, fp32 and two-byte operands.  Pattern, v [N, H, F], bias (NULL, [nnz] with
+ * bias_heads = 1 or [nnz, H] with bias_heads = H), out, stat, the forms, the long-row plan and the
+ * workspace (psa_attention_workspace_bytes(nnz, H, F); 0 bytes, NULL allowed, when nnz <= 128) are
+ * those of psa_attention_fw / psa_attention_bw_entries; a_row [M, H] and a_col [N, H] hold one scalar
+ * per node and head and take the place of q and k; H, F >= 1.
+ *   z[e, h]      = (a_row[row(e), h] + a_col[col[e], h]) (+ bias)        (two rounded additions, the
+ *                                                                        second skipped without a bias)
+ *   s[e, h]      = z > 0 ? z : negative_slope * z                        (one rounded product; z == 0
+ *                                                                        and a NaN take the slope branch)
+ *   p, stat      = the row softmax of s and its {m, l}, as psa_attention_fw (of s after the activation)
+ *   out[r, h, :] = inv_keep * sum_{e in row r} keep(e, h) * p[e, h] * v[col[e], h, :]
+ * The dropout arguments are always present: T, keep(e, h) and inv_keep are those of
+ * psa_attention_dropout_fw (the same entries dropped for the same seed, psa_attention_dropout_mask
+ * gives the mask); dropout_p = 0 keeps everything and multiplies by 1, the bits of the maskless
+ * computation, and the seed is then ignored.  No contraction in z and s, so the backward recomputes
+ * the same bits.  negative_slope must be finite (else PSA_ERR_INVALID_ARG); it may be 0 or negative.
+ *   psa_gat_attention_bw_entries  with D = keep * inv_keep (1 without dropout), delta = <grad_out, out>
+ *                                 and dP = <grad_out[row(e), h, :], v[col[e], h, :]>: writes
+ *                                 p * D [nnz, H] and dz [nnz, H] = p * (D * dP - delta) *
+ *                                 (z > 0 ? 1 : negative_slope); a row without entries writes
+ *                                 nothing.  grad_a_row is the sum of dz over the entries of a row,
+ *                                 grad_a_col over those of a column, grad_v = (p, grad_out) over the CSC
+ *                                 view (psa_spmm_heads), grad_bias = dz (summed over the heads for
+ *                                 bias_heads = 1).
+ * Non-finite values by plain IEEE arithmetic, as psa_attention_fw: a NaN, a +inf or nothing but -inf
+ * among the scores of a row and head is NaN in out[r, h, :]; -inf among finite scores has weight
+ * exactly 0.  A -inf bias therefore masks its entry for negative_slope > 0; with negative_slope == 0
+ * it gives 0 * -inf = NaN and poisons its row and head (not special-cased).
+ * a_row and a_col are read with element loads at any element alignment; the 16-byte form of v, out
+ * (and grad_out) needs F % 4 == 0 (two-byte operands: F % 8 == 0) and 16-byte alignment of those
+ * three, any element alignment is served otherwise.  Every address is formed in 64-bit arithmetic.
+ * No float atomics, no host read: bitwise reproducible and capturable.
+ *   psa_gat_attention_half_*      dtype names the format of a_row, a_col, v, out and grad_out
+ *                                 (PSA_BF16 is served): half-width loads, every sum, the activation,
+ *                                 the softmax and stat fp32, out rounded once; bias, p and dz fp32. */
+int psa_gat_attention_fw(const int64_t* rowptr, const int64_t* col, const float* a_row, const float* a_col,
+                         const float* v, const float* bias, int64_t bias_heads, float negative_slope, double dropout_p,
+                         uint64_t seed, int64_t M, int64_t N, int64_t H, int64_t F, int64_t nnz, float* out,
+                         float* stat, void* workspace, size_t workspace_bytes, psa_stream_t stream);
+int psa_gat_attention_bw_entries(const int64_t* rowptr, const int64_t* col, const float* a_row, const float* a_col,
+                                 const float* v, const float* bias, int64_t bias_heads, float negative_slope,
+                                 double dropout_p, uint64_t seed, const float* grad_out, const float* out,
+                                 const float* stat, int64_t M, int64_t N, int64_t H, int64_t F, int64_t nnz, float* p,
+                                 float* dz, void* workspace, size_t workspace_bytes, psa_stream_t stream);
+int psa_gat_attention_half_fw(int dtype, const int64_t* rowptr, const int64_t* col, const void* a_row,
+                              const void* a_col, const void* v, const float* bias, int64_t bias_heads,
+                              float negative_slope, double dropout_p, uint64_t seed, int64_t M, int64_t N, int64_t H,
+                              int64_t F, int64_t nnz, void* out, float* stat, void* workspace, size_t workspace_bytes,
+                              psa_stream_t stream);
+int psa_gat_attention_half_bw_entries(int dtype, const int64_t* rowptr, const int64_t* col, const void* a_row,
+                                      const void* a_col, const void* v, const float* bias, int64_t bias_heads,
+                                      float negative_slope, double dropout_p, uint64_t seed, const void* grad_out,
+                                      const void* out, const float* stat, int64_t M, int64_t N, int64_t H, int64_t F,
+                                      int64_t nnz, float* p, float* dz, void* workspace, size_t workspace_bytes,
+                                      psa_stream_t stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -66,6 +66,7 @@ if not _running_the_builder():
         ("softmax", ("softmax",)),
         ("sddmm", ("sddmm",)),
         ("attention", ("attention",)),
+        ("gat", ("gat_attention",)),
     )
 
     __all__ = ["__version__"]

@@ -196,6 +196,21 @@ SIGNATURES = {
                                                       c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
                                                       c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "psa_attention_dropout_mask": (c_int, [c_int64, c_int64, c_double, c_uint64, c_void_p, c_void_p]),
+    # GAT scores: (a_row, a_col) for (q, k), (float negative_slope, double dropout_p, uint64_t seed) for scale, no K
+    "psa_gat_attention_fw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float,
+                                     c_double, c_uint64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
+                                     c_void_p, c_void_p, c_size_t, c_void_p]),
+    "psa_gat_attention_bw_entries": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                             c_float, c_double, c_uint64, c_void_p, c_void_p, c_void_p, c_int64,
+                                             c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                             c_size_t, c_void_p]),
+    "psa_gat_attention_half_fw": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                          c_float, c_double, c_uint64, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                          c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "psa_gat_attention_half_bw_entries": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_int64, c_float, c_double, c_uint64, c_void_p, c_void_p, c_void_p,
+                                                  c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
+                                                  c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

@@ -8,6 +8,9 @@
 //                                  from the saved, rounded out
 //   psa_attention_half_dropout_fw / _bw_entries  the same with dropout of the weights (attention_dropout.h):
 //                                  inv_keep is applied in fp32 before the one rounding
+//   psa_gat_attention_half_fw / _bw_entries  the additive scores of a GAT layer (attention.hip: A::kGat) with
+//                                  a_row, a_col, v two-byte: element loads widened exactly, sums, the activation
+//                                  and the softmax fp32; dZ is written where dS was
 //
 // Plan (attention.hip, unchanged): one wave per CSR row, 64-entry tiles, scores through the per-wave LDS tile
 // of 64 x Hb floats, online softmax per lane group, rows above psa::kLongRow entries as 128-entry chunks whose
@@ -172,6 +175,34 @@ __device__ __forceinline__ void dots_tile(const elem_t* __restrict__ y, const el
   }
 }
 
+// ---- additive scores of a GAT layer: stage (a) without a dot ---------------------------------------
+
+// s of z: z itself where z > 0, the rounded product otherwise (z == 0 and a NaN take the slope branch).
+__device__ __forceinline__ float gat_act(float z, float slope) { return z > 0.f ? z : __fmul_rn(slope, z); }
+
+// tile[idx * Hb + h] = s (ACT) or z, with z = (a_row[row, h] + a_col[c(idx), h]) (+ bias) in fp32, for the
+// n <= 64 entries from base on and the Hs heads from hb on; no contraction, so forward and backward agree bit
+// for bit.  Lane t takes (idx, h) = (t / Hs, t % Hs) for t = lane, lane + 64, ...: the mapping of
+// attn_bw_range's consumer loop.  2-byte loads at any element alignment.
+template <class A, typename T, bool ACT>
+__device__ __forceinline__ void gat_tile(const A& a, int64_t row, int64_t hb, int Hs, int64_t c_l, int n,
+                                         int64_t base, int lane, float* __restrict__ tile) {
+  const int total = n * Hs;
+  for (int t0 = 0; t0 < total; t0 += 64) {  // wave-uniform trips: the shuffle reads every lane's c_l
+    const int t = t0 + lane;
+    const bool ok = t < total;
+    const int idx = ok ? t / Hs : 0;
+    const int h = t - idx * Hs;
+    const int64_t c = __shfl(static_cast<long long>(c_l), idx);
+    if (ok) {
+      const int64_t hh = hb + h;
+      float z = __fadd_rn(psa_half::widen1<T>(a.a_row, row * a.H + hh), psa_half::widen1<T>(a.a_col, c * a.H + hh));
+      if (a.bias) z = __fadd_rn(z, a.bias[(base + idx) * a.bias_heads + (a.bias_heads == 1 ? 0 : hh)]);
+      tile[idx * a.Hb + h] = ACT ? gat_act(z, a.slope) : z;
+    }
+  }
+}
+
 // ---- forward --------------------------------------------------------------------------------------
 
 struct FwArgs {
@@ -189,12 +220,24 @@ struct FwArgs {
   int P, shift;  // lanes per entry in the aggregation
   int ntiles;   // tiles of P * VEC elements over Hb * F
   static constexpr bool kDrop = false;
+  static constexpr bool kGat = false;
 };
 
 // The dropout forms of the kernels take their arguments with the mask's parameters behind them; the plain
 // forms never see them (every use sits under if constexpr (A::kDrop)).
 struct FwDropArgs : FwArgs {
   static constexpr bool kDrop = true;
+  psa::Drop drop;
+};
+
+// The GAT forms: q, k, scale, K and dot are not used (every use sits under if constexpr (!A::kGat)).
+template <bool DROP>
+struct GatFwArgs : FwArgs {
+  static constexpr bool kDrop = DROP;
+  static constexpr bool kGat = true;
+  const elem_t* a_row;  // [M, H]
+  const elem_t* a_col;  // [N, H]
+  float slope;
   psa::Drop drop;
 };
 
@@ -225,8 +268,12 @@ __device__ __forceinline__ void attn_range(const A& a, int64_t row, int hb, int 
   const int G = 64 >> a.shift;
   const int64_t Ds = static_cast<int64_t>(Hs) * a.F;
   const int64_t vstride = a.H * a.F;
-  const elem_t* __restrict__ qrow = a.q + row * a.dot.stride + static_cast<int64_t>(hb) * a.K;
-  const elem_t* __restrict__ kb = a.k + static_cast<int64_t>(hb) * a.K;
+  const elem_t* __restrict__ qrow = nullptr;
+  const elem_t* __restrict__ kb = nullptr;
+  if constexpr (!A::kGat) {
+    qrow = a.q + row * a.dot.stride + static_cast<int64_t>(hb) * a.K;
+    kb = a.k + static_cast<int64_t>(hb) * a.K;
+  }
   const elem_t* __restrict__ vb = a.v + static_cast<int64_t>(hb) * a.F;
   const int bhstep = a.bias_heads == 1 ? 0 : 1;
   const float* __restrict__ biasb = a.bias ? a.bias + (bhstep ? hb : 0) : nullptr;
@@ -244,14 +291,18 @@ __device__ __forceinline__ void attn_range(const A& a, int64_t row, int hb, int 
     for (int i = 0; i < VEC; ++i) acc[t][i] = 0.f;
   }
   float xr[NR > 0 ? NR : 1][VEC];
-  load_slices<T, VEC, NR>(qrow, a.dot, Hs, lane, xr);
+  if constexpr (!A::kGat) load_slices<T, VEC, NR>(qrow, a.dot, Hs, lane, xr);
   for (int64_t base = s; base < e; base += 64) {
     const int n = (e - base) < 64 ? static_cast<int>(e - base) : 64;
     int64_t c_l = 0;
     if (lane < n) c_l = a.col[base + lane];
     wave_sync();  // the previous tile has been consumed
-    dots_tile<T, VEC, NR>(kb, qrow, xr, a.dot, Hs, c_l, n, lane, a.scale,
-                          biasb ? biasb + base * a.bias_heads : nullptr, a.bias_heads, bhstep, tile, a.Hb);
+    if constexpr (A::kGat) {
+      gat_tile<A, T, true>(a, row, hb, Hs, c_l, n, base, lane, tile);
+    } else {
+      dots_tile<T, VEC, NR>(kb, qrow, xr, a.dot, Hs, c_l, n, lane, a.scale,
+                            biasb ? biasb + base * a.bias_heads : nullptr, a.bias_heads, bhstep, tile, a.Hb);
+    }
     if constexpr (A::kDrop) {  // one draw per (entry, head): lane i draws for entry base + i, a ballot per head
       const uint64_t stream = psa::rand_stream(a.drop.seed, base + lane);
       for (int h = 0; h < Hs; ++h) {
@@ -495,6 +546,7 @@ struct BwArgs {
   float* p;
   float* ds;
   static constexpr bool kDrop = false;
+  static constexpr bool kGat = false;
 };
 
 struct BwDropArgs : BwArgs {
@@ -502,8 +554,21 @@ struct BwDropArgs : BwArgs {
   psa::Drop drop;
 };
 
+// The GAT forms: ds receives dZ; q, k, scale, K and dot are not used.
+template <bool DROP>
+struct GatBwArgs : BwArgs {
+  static constexpr bool kDrop = DROP;
+  static constexpr bool kGat = true;
+  const elem_t* a_row;
+  const elem_t* a_col;
+  float slope;
+  psa::Drop drop;
+};
+
 // p and dS of the entries [s, e) of one row.  Dropout, with D = keep * inv_keep recomputed per (entry, head)
 // by the lane that writes it: p * D where p is written, and dS = p * (D * dP - delta).
+// GAT: tile_s receives z (gat_tile, NRK = 0); the consumer applies the activation, so that it has the sign of z
+// for dZ = dS * (z > 0 ? 1 : slope), rounded once more.
 template <class A, typename T, int VEC, int NRK, int NRF>
 __device__ __forceinline__ void attn_bw_range(const A& a, int64_t row, int64_t s, int64_t e, int lane,
                                               float* __restrict__ tile_s, float* __restrict__ tile_p,
@@ -511,11 +576,12 @@ __device__ __forceinline__ void attn_bw_range(const A& a, int64_t row, int64_t s
   const int bhstep = a.bias_heads == 1 ? 0 : 1;
   for (int64_t hb = 0; hb < a.H; hb += a.Hb) {
     const int Hs = a.H - hb < a.Hb ? static_cast<int>(a.H - hb) : a.Hb;
-    const elem_t* __restrict__ qrow = a.q + row * a.dot.stride + hb * a.K;
+    const elem_t* __restrict__ qrow = nullptr;
+    if constexpr (!A::kGat) qrow = a.q + row * a.dot.stride + hb * a.K;
     const elem_t* __restrict__ grow = a.grad_out + row * a.dotf.stride + hb * a.F;
     const float* __restrict__ biasb = a.bias ? a.bias + (bhstep ? hb : 0) : nullptr;
     float xq[NRK > 0 ? NRK : 1][VEC], xg[NRF > 0 ? NRF : 1][VEC];
-    load_slices<T, VEC, NRK>(qrow, a.dot, Hs, lane, xq);
+    if constexpr (!A::kGat) load_slices<T, VEC, NRK>(qrow, a.dot, Hs, lane, xq);
     load_slices<T, VEC, NRF>(grow, a.dotf, Hs, lane, xg);
     wave_sync();  // the previous head block has been consumed
     // delta[h] = <grad_out[row, h, :], out[row, h, :]>: the row of the saved (rounded) out as the one gathered row
@@ -524,25 +590,36 @@ __device__ __forceinline__ void attn_bw_range(const A& a, int64_t row, int64_t s
       const int n = (e - base) < 64 ? static_cast<int>(e - base) : 64;
       int64_t c_l = 0;
       if (lane < n) c_l = a.col[base + lane];
-      dots_tile<T, VEC, NRK>(a.k + hb * a.K, qrow, xq, a.dot, Hs, c_l, n, lane, a.scale,
-                             biasb ? biasb + base * a.bias_heads : nullptr, a.bias_heads, bhstep, tile_s, a.Hb);
+      if constexpr (A::kGat) {
+        gat_tile<A, T, false>(a, row, hb, Hs, c_l, n, base, lane, tile_s);
+      } else {
+        dots_tile<T, VEC, NRK>(a.k + hb * a.K, qrow, xq, a.dot, Hs, c_l, n, lane, a.scale,
+                               biasb ? biasb + base * a.bias_heads : nullptr, a.bias_heads, bhstep, tile_s, a.Hb);
+      }
       dots_tile<T, VEC, NRF>(a.v + hb * a.F, grow, xg, a.dotf, Hs, c_l, n, lane, 1.f, nullptr, 0, 0, tile_p, a.Hb);
       wave_sync();
       for (int t = lane; t < n * Hs; t += 64) {
         const int idx = t / Hs;
         const int h = t - idx * Hs;
         const float m = a.stat[(row * a.H + hb + h) * 2], l = a.stat[(row * a.H + hb + h) * 2 + 1];
-        const float pe = expf(tile_s[idx * a.Hb + h] - m) / l;
+        float sc = tile_s[idx * a.Hb + h], fac = 1.f;
+        if constexpr (A::kGat) {
+          fac = sc > 0.f ? 1.f : a.slope;
+          sc = gat_act(sc, a.slope);
+        }
+        const float pe = expf(sc - m) / l;
         const int64_t at = (base + idx) * a.H + hb + h;
+        float dse;
         if constexpr (A::kDrop) {
           const bool kept = psa::keep_of(psa::rand_stream(a.drop.seed, base + idx), hb + h, a.drop.T);
           const float dk = kept ? a.drop.inv_keep : 0.f;
           a.p[at] = __fmul_rn(pe, dk);
-          a.ds[at] = pe * (__fmul_rn(dk, tile_p[idx * a.Hb + h]) - delta[h]);
+          dse = pe * (__fmul_rn(dk, tile_p[idx * a.Hb + h]) - delta[h]);
         } else {
           a.p[at] = pe;
-          a.ds[at] = pe * (tile_p[idx * a.Hb + h] - delta[h]);
+          dse = pe * (tile_p[idx * a.Hb + h] - delta[h]);
         }
+        a.ds[at] = A::kGat ? __fmul_rn(dse, fac) : dse;
       }
       wave_sync();  // before the next tile overwrites
     }
@@ -828,6 +905,140 @@ int attention_bw(const char* who, const psa::Drop& drop, int dtype, const int64_
 #undef PSA_ATTN_BW
 }
 
+// ---- GAT: the same launches without the slices of q (NR = NRK = 0) --------------------------------
+
+// Everything of the argument struct that the dot-product scores alone use.
+template <class A>
+void gat_no_dot(A* a) {
+  a->q = nullptr;
+  a->k = nullptr;
+  a->scale = 1.f;
+  a->K = 1;
+  a->dot = DotGeo{};
+}
+
+template <bool DROP>
+int gat_fw(const char* who, const psa::Drop& drop, int dtype, const int64_t* rowptr, const int64_t* col,
+           const void* a_row, const void* a_col, const void* v, const float* bias, int64_t bias_heads, float slope,
+           int64_t M, int64_t N, int64_t H, int64_t F, int64_t nnz, void* out, float* stat, void* workspace,
+           size_t workspace_bytes, psa_stream_t stream) {
+  using A = GatFwArgs<DROP>;
+  ATTN_REQUIRE(dtype == PSA_BF16, "dtype must be PSA_BF16");
+  ATTN_REQUIRE(M >= 0 && N >= 0 && nnz >= 0, "negative size");
+  ATTN_REQUIRE(H >= 1 && F >= 1, "H and F must be at least 1");
+  ATTN_REQUIRE(nnz < (int64_t{1} << 38), "nnz too large");
+  ATTN_REQUIRE(H < (int64_t{1} << 24) && F < (int64_t{1} << 24), "H or F too large");
+  ATTN_REQUIRE(bias == nullptr || bias_heads == 1 || bias_heads == H, "bias_heads must be 1 or H");
+  ATTN_REQUIRE(std::isfinite(slope), "negative_slope must be finite");
+  if (M == 0) return PSA_OK;
+  ATTN_REQUIRE(rowptr && out && stat, "NULL pointer");
+  ATTN_REQUIRE(nnz == 0 || (col && a_row && a_col && v), "NULL pointer");
+  ATTN_REQUIRE(psa::aligned(a_row, 2) && psa::aligned(a_col, 2) && psa::aligned(v, 2) && psa::aligned(out, 2),
+              "operands must be 2-byte aligned");
+  hipStream_t s = psa::as_stream(stream);
+  unsigned long long* ctr = nullptr;
+  psa::LongEntry* list = nullptr;
+  float *part = nullptr, *pstat = nullptr;
+  if (nnz > psa::kLongRow) {
+    const int rc = take_list(who, workspace, workspace_bytes,
+                             psa_attention_workspace_bytes(nnz, H, F), s, &ctr, &list);
+    if (rc != PSA_OK) return rc;
+    char* w = static_cast<char*>(workspace) + psa::long_list_bytes(nnz);
+    part = reinterpret_cast<float*>(w);
+    pstat = reinterpret_cast<float*>(w + part_bytes(nnz, H * F));
+  }
+  const bool v8 = (F % 8 == 0) && psa::aligned(v, 16) && psa::aligned(out, 16);
+  const int vec = v8 ? 8 : 1;
+  A a;
+  gat_no_dot(&a);
+  a.drop = drop;
+  a.rowptr = rowptr;
+  a.col = col;
+  a.a_row = elems(a_row);
+  a.a_col = elems(a_col);
+  a.slope = slope;
+  a.v = elems(v);
+  a.bias = bias;
+  a.bias_heads = bias ? bias_heads : 1;
+  a.M = M;
+  a.H = H;
+  a.F = F;
+  a.nnz = nnz;
+  a.Hb = head_block(H, F, vec);
+  const int64_t Db = static_cast<int64_t>(a.Hb) * F;
+  a.P = pow2_at_least(psa::ceil_div(Db, vec), 64, &a.shift);
+  const int64_t ntiles = psa::ceil_div(Db, static_cast<int64_t>(a.P) * vec);
+  a.ntiles = static_cast<int>(ntiles);
+  elem_t* o = static_cast<elem_t*>(out);
+#define PSA_GAT_FW(VEC, NT) return launch_fw<A, BF16, VEC, 0, NT>(a, o, stat, ctr, list, part, pstat, s)
+  if (v8) {
+    if (ntiles == 1) PSA_GAT_FW(8, 1);
+    PSA_GAT_FW(8, 2);
+  }
+  if (ntiles == 1) PSA_GAT_FW(1, 1);
+  if (ntiles == 2) PSA_GAT_FW(1, 2);
+  PSA_GAT_FW(1, 4);
+#undef PSA_GAT_FW
+}
+
+template <bool DROP>
+int gat_bw(const char* who, const psa::Drop& drop, int dtype, const int64_t* rowptr, const int64_t* col,
+           const void* a_row, const void* a_col, const void* v, const float* bias, int64_t bias_heads, float slope,
+           const void* grad_out, const void* out, const float* stat, int64_t M, int64_t N, int64_t H, int64_t F,
+           int64_t nnz, float* p, float* dz, void* workspace, size_t workspace_bytes, psa_stream_t stream) {
+  using A = GatBwArgs<DROP>;
+  ATTN_REQUIRE(dtype == PSA_BF16, "dtype must be PSA_BF16");
+  ATTN_REQUIRE(M >= 0 && N >= 0 && nnz >= 0, "negative size");
+  ATTN_REQUIRE(H >= 1 && F >= 1, "H and F must be at least 1");
+  ATTN_REQUIRE(nnz < (int64_t{1} << 38), "nnz too large");
+  ATTN_REQUIRE(H < (int64_t{1} << 24) && F < (int64_t{1} << 24), "H or F too large");
+  ATTN_REQUIRE(bias == nullptr || bias_heads == 1 || bias_heads == H, "bias_heads must be 1 or H");
+  ATTN_REQUIRE(std::isfinite(slope), "negative_slope must be finite");
+  if (M == 0 || nnz == 0) return PSA_OK;
+  ATTN_REQUIRE(rowptr && col && a_row && a_col && v && grad_out && out && stat && p && dz, "NULL pointer");
+  ATTN_REQUIRE(psa::aligned(a_row, 2) && psa::aligned(a_col, 2) && psa::aligned(v, 2) && psa::aligned(grad_out, 2) &&
+                  psa::aligned(out, 2),
+              "operands must be 2-byte aligned");
+  hipStream_t s = psa::as_stream(stream);
+  unsigned long long* ctr = nullptr;
+  psa::LongEntry* list = nullptr;
+  if (nnz > psa::kLongRow) {
+    const int rc = take_list(who, workspace, workspace_bytes, psa::long_list_bytes(nnz), s, &ctr, &list);
+    if (rc != PSA_OK) return rc;
+  }
+  const bool v8 = (F % 8 == 0) && psa::aligned(v, 16) && psa::aligned(grad_out, 16) && psa::aligned(out, 16);
+  const int vec = v8 ? 8 : 1;
+  A a;
+  gat_no_dot(&a);
+  a.drop = drop;
+  a.rowptr = rowptr;
+  a.col = col;
+  a.a_row = elems(a_row);
+  a.a_col = elems(a_col);
+  a.slope = slope;
+  a.v = elems(v);
+  a.bias = bias;
+  a.bias_heads = bias ? bias_heads : 1;
+  a.grad_out = elems(grad_out);
+  a.out = elems(out);
+  a.stat = stat;
+  a.M = M;
+  a.H = H;
+  a.F = F;
+  a.nnz = nnz;
+  a.Hb = static_cast<int>(H < kHeadBlock ? H : kHeadBlock);
+  a.dotf = dot_geo(H, a.Hb, F, vec);
+  a.p = p;
+  a.ds = dz;
+  const bool rf = a.dotf.nit <= kMaxTiles;
+  if (v8) {
+    if (rf) return launch_bw<A, BF16, 8, 0, 4>(a, ctr, list, s);
+    return launch_bw<A, BF16, 8, 0, 0>(a, ctr, list, s);
+  }
+  if (rf) return launch_bw<A, BF16, 1, 0, 4>(a, ctr, list, s);
+  return launch_bw<A, BF16, 1, 0, 0>(a, ctr, list, s);
+}
+
 #undef ATTN_REQUIRE
 
 }  // namespace
@@ -874,6 +1085,39 @@ int psa_attention_half_dropout_bw_entries(int dtype, const int64_t* rowptr, cons
   return attention_bw<BwDropArgs>("psa_attention_half_dropout_bw_entries", drop, dtype, rowptr, col, q, k, v, bias,
                                   bias_heads, scale, grad_out, out, stat, M, N, H, K, F, nnz, p, ds, workspace,
                                   workspace_bytes, stream);
+}
+
+// dropout_p == 0 takes the maskless instantiations: the same bits (every entry kept, times 1) without the draws.
+int psa_gat_attention_half_fw(int dtype, const int64_t* rowptr, const int64_t* col, const void* a_row,
+                              const void* a_col, const void* v, const float* bias, int64_t bias_heads,
+                              float negative_slope, double dropout_p, uint64_t seed, int64_t M, int64_t N, int64_t H,
+                              int64_t F, int64_t nnz, void* out, float* stat, void* workspace, size_t workspace_bytes,
+                              psa_stream_t stream) {
+  psa::Drop drop;
+  if (!psa::make_drop("psa_gat_attention_half_fw", dropout_p, seed, &drop)) return PSA_ERR_INVALID_ARG;
+  if (dropout_p == 0.0) {
+    return gat_fw<false>("psa_gat_attention_half_fw", drop, dtype, rowptr, col, a_row, a_col, v, bias, bias_heads,
+                         negative_slope, M, N, H, F, nnz, out, stat, workspace, workspace_bytes, stream);
+  }
+  return gat_fw<true>("psa_gat_attention_half_fw", drop, dtype, rowptr, col, a_row, a_col, v, bias, bias_heads,
+                      negative_slope, M, N, H, F, nnz, out, stat, workspace, workspace_bytes, stream);
+}
+
+int psa_gat_attention_half_bw_entries(int dtype, const int64_t* rowptr, const int64_t* col, const void* a_row,
+                                      const void* a_col, const void* v, const float* bias, int64_t bias_heads,
+                                      float negative_slope, double dropout_p, uint64_t seed, const void* grad_out,
+                                      const void* out, const float* stat, int64_t M, int64_t N, int64_t H, int64_t F,
+                                      int64_t nnz, float* p, float* dz, void* workspace, size_t workspace_bytes,
+                                      psa_stream_t stream) {
+  psa::Drop drop;
+  if (!psa::make_drop("psa_gat_attention_half_bw_entries", dropout_p, seed, &drop)) return PSA_ERR_INVALID_ARG;
+  if (dropout_p == 0.0) {
+    return gat_bw<false>("psa_gat_attention_half_bw_entries", drop, dtype, rowptr, col, a_row, a_col, v, bias,
+                         bias_heads, negative_slope, grad_out, out, stat, M, N, H, F, nnz, p, dz, workspace,
+                         workspace_bytes, stream);
+  }
+  return gat_bw<true>("psa_gat_attention_half_bw_entries", drop, dtype, rowptr, col, a_row, a_col, v, bias, bias_heads,
+                      negative_slope, grad_out, out, stat, M, N, H, F, nnz, p, dz, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

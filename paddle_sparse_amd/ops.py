@@ -2094,3 +2094,182 @@ def attention(rowptr: torch.Tensor, col: torch.Tensor, q: torch.Tensor, k: torch
     else:
         out = _attention_fw_raw(rowptr, col, q, k, v, bias, scale, dropout_p, seed)[0]
     return out[:, 0] if flat else out
+
+
+# ---- fused GAT attention: additive LeakyReLU scores in the one-pass kernels (csrc/attention.hip, A::kGat) ----
+
+def _slope_arg(negative_slope, who: str = "gat_attention") -> float:
+    """negative_slope checked: a finite Python number (0 and negative slopes are served)."""
+    if isinstance(negative_slope, bool) or not isinstance(negative_slope, (int, float)):
+        raise TypeError(f"{who}: negative_slope must be a float (got {type(negative_slope).__name__})")
+    negative_slope = float(negative_slope)
+    if negative_slope != negative_slope or negative_slope in (float("inf"), float("-inf")):
+        raise ValueError(f"{who}: negative_slope must be finite (got {negative_slope})")
+    return negative_slope
+
+
+def _gat_operands(rowptr, col, a_row, a_col, v, bias):
+    """The checked, contiguous operands in heads form (a_row [M, H], a_col [N, H], v [N, H, F]) and whether the
+    caller gave the one-head form.  Nothing is copied for alignment: the kernels take the element form for a v that
+    does not start on 16 bytes."""
+    rowptr, col, M, nnz = _heads_pattern(rowptr, col)
+    a_row, a_col, v = _attention_dense(a_row, "a_row"), _attention_dense(a_col, "a_col"), _attention_dense(v, "v")
+    if not (a_row.dtype == a_col.dtype == v.dtype):
+        raise TypeError(f"gat_attention: a_row, a_col, v must share one dtype (got {a_row.dtype}, {a_col.dtype}, "
+                        f"{v.dtype})")
+    dims = (a_row.dim(), a_col.dim(), v.dim())
+    if dims not in ((1, 1, 2), (2, 2, 3)):
+        raise ValueError(f"gat_attention: a_row, a_col, v must be [M], [N], [N, F] or [M, H], [N, H], [N, H, F] "
+                         f"(got {tuple(a_row.shape)}, {tuple(a_col.shape)}, {tuple(v.shape)})")
+    flat = v.dim() == 2
+    if flat:
+        a_row, a_col, v = a_row.unsqueeze(1), a_col.unsqueeze(1), v.unsqueeze(1)
+    N, H, F = v.shape
+    if a_row.shape != (M, H) or a_col.shape != (N, H):
+        raise ValueError(f"gat_attention: a_row must be [{M}, H], a_col [N, H] and v [N, H, F] "
+                         f"(got {tuple(a_row.shape)}, {tuple(a_col.shape)}, {tuple(v.shape)})")
+    if H < 1 or F < 1:
+        raise ValueError("gat_attention: H and F must be at least 1")
+    if bias is not None:
+        bias = _f32(bias, "bias")
+        if bias.shape not in ((nnz,), (nnz, H)):
+            raise ValueError(f"gat_attention: bias must be [{nnz}] or [{nnz}, {H}] (got {tuple(bias.shape)})")
+    return rowptr, col, a_row, a_col, v, bias, flat
+
+
+def _gat_fw_raw(rowptr, col, a_row, a_col, v, bias, slope: float, dropout_p: float = 0.0, seed: int = 0):
+    """(out [M, H, F], stat [M, H, 2]) from checked heads-form operands."""
+    M, H = a_row.shape
+    N, F, nnz = v.shape[0], v.shape[2], col.numel()
+    out = torch.empty((M, H, F), dtype=v.dtype, device=v.device)
+    stat = torch.empty((M, H, 2), dtype=torch.float32, device=v.device)
+    lib = _lib.load()
+    ws_bytes = lib.psa_attention_workspace_bytes(nnz, H, F)
+    ws = _workspace(ws_bytes, v.device) if ws_bytes else None
+    with _on(v.device):
+        if v.dtype == torch.float32:
+            check(lib.psa_gat_attention_fw(_ptr(rowptr), _ptr(col), _ptr(a_row), _ptr(a_col), _ptr(v), _ptr(bias),
+                                           _bias_heads(bias), slope, dropout_p, seed, M, N, H, F, nnz, _ptr(out),
+                                           _ptr(stat), _ptr(ws), ws_bytes, _stream()))
+        else:
+            check(lib.psa_gat_attention_half_fw(_DTYPE_ID[v.dtype], _ptr(rowptr), _ptr(col), _ptr(a_row), _ptr(a_col),
+                                                _ptr(v), _ptr(bias), _bias_heads(bias), slope, dropout_p, seed, M, N, H,
+                                                F, nnz, _ptr(out), _ptr(stat), _ptr(ws), ws_bytes, _stream()))
+    return out, stat
+
+
+def _gat_bw_entries_raw(rowptr, col, a_row, a_col, v, bias, slope: float, grad_out, out, stat, dropout_p: float = 0.0,
+                        seed: int = 0):
+    """(p * D [nnz, H], dZ [nnz, H]) with D = keep * inv_keep (1 without dropout): the per-entry half of the
+    backward, from the saved {m, l}."""
+    M, H = a_row.shape
+    N, F, nnz = v.shape[0], v.shape[2], col.numel()
+    if grad_out.dtype != v.dtype:
+        raise TypeError(f"gat_attention: grad_out must be {v.dtype} as a_row, a_col, v (got {grad_out.dtype})")
+    p = torch.empty((nnz, H), dtype=torch.float32, device=v.device)
+    dz = torch.empty((nnz, H), dtype=torch.float32, device=v.device)
+    lib = _lib.load()
+    ws_bytes = lib.psa_attention_workspace_bytes(nnz, H, F)
+    ws = _workspace(ws_bytes, v.device) if ws_bytes else None
+    with _on(v.device):
+        if v.dtype == torch.float32:
+            check(lib.psa_gat_attention_bw_entries(_ptr(rowptr), _ptr(col), _ptr(a_row), _ptr(a_col), _ptr(v),
+                                                   _ptr(bias), _bias_heads(bias), slope, dropout_p, seed, _ptr(grad_out),
+                                                   _ptr(out), _ptr(stat), M, N, H, F, nnz, _ptr(p), _ptr(dz), _ptr(ws),
+                                                   ws_bytes, _stream()))
+        else:
+            check(lib.psa_gat_attention_half_bw_entries(_DTYPE_ID[v.dtype], _ptr(rowptr), _ptr(col), _ptr(a_row),
+                                                        _ptr(a_col), _ptr(v), _ptr(bias), _bias_heads(bias), slope,
+                                                        dropout_p, seed, _ptr(grad_out), _ptr(out), _ptr(stat), M, N, H,
+                                                        F, nnz, _ptr(p), _ptr(dz), _ptr(ws), ws_bytes, _stream()))
+    return p, dz
+
+
+def gat_attention_raw(rowptr, col, a_row, a_col, v, bias=None, negative_slope: float = 0.2, dropout_p: float = 0.0,
+                      seed: int = 0):
+    """The forward alone, without autograd: (out, stat) with stat [M, H, 2] = {m, l} of the scores after the
+    activation (one-head operands: [M, 2]).  dropout_p > 0 needs the seed as an int (gat_attention_bw takes the same)."""
+    rowptr, col, a_row, a_col, v, bias, flat = _gat_operands(rowptr, col, a_row, a_col, v, bias)
+    slope = _slope_arg(negative_slope)
+    dropout_p, seed = _dropout_args(dropout_p, seed, "gat_attention", draw=False)
+    out, stat = _gat_fw_raw(rowptr, col, a_row.detach(), a_col.detach(), v.detach(),
+                            None if bias is None else bias.detach(), slope, dropout_p, seed)
+    return (out[:, 0], stat[:, 0]) if flat else (out, stat)
+
+
+def gat_attention_bw(rowptr, col, a_row, a_col, v, bias, negative_slope: float, grad_out, out, stat, csc=None,
+                     want=(True, True, True, True), dropout_p: float = 0.0, seed: int = 0):
+    """(grad_a_row, grad_a_col, grad_v, grad_bias) of gat_attention from what its forward left (heads-form operands,
+    out and stat of gat_attention_raw); None where `want` says so.  p and dZ [nnz, H] live only inside this call.
+    The sums of dZ are fp32 (psa_segment_reduce, in entry order) and rounded once for bfloat16 operands; the CSC view
+    is asked for only by the gradients of a_col and v."""
+    want_r, want_c, want_v, want_b = want
+    grad_out = grad_out.contiguous()
+    slope = _slope_arg(negative_slope)
+    dropout_p, seed = _dropout_args(dropout_p, seed, "gat_attention", draw=False)
+    p, dz = _gat_bw_entries_raw(rowptr, col, a_row, a_col, v, bias, slope, grad_out, out, stat, dropout_p, seed)
+    grad_r = grad_c = grad_v = grad_b = None
+    if want_r:  # grad_a_row[r, h] = sum over the row's entries of dZ[e, h]
+        grad_r = _segment_csr_raw(dz, rowptr, "sum").to(a_row.dtype)
+    if want_c or want_v:
+        colptr, row_csc, csr2csc = csc = _csc_view(csc, rowptr, col, v.shape[0])
+        if want_c:  # grad_a_col[c, h] = sum over the column's entries of dZ[e, h]
+            grad_c = _segment_csr_raw(dz, colptr, "sum", perm=csr2csc).to(a_col.dtype)
+        if want_v:  # grad_v[c, h] = sum over the column's entries of (p * D)[e, h] * grad_out[row(e), h]
+            if v.dtype != torch.float32:
+                grad_v = spmm_heads_half_raw(colptr, row_csc, _gather_rows_raw(p, csr2csc), grad_out, 1.0)
+            else:
+                grad_v = _spmm_heads_transposed(csc, p, grad_out)
+    if want_b and bias is not None:
+        grad_b = dz.sum(dim=1) if bias.dim() == 1 else dz
+    return grad_r, grad_c, grad_v, grad_b
+
+
+class _GatAttention(torch.autograd.Function):
+    """Heads-form operands, already checked.  Saves a_row, a_col, v, out, stat and the caller's bias: no tensor with
+    nnz rows of its own (the pattern is the caller's and rides on ctx)."""
+
+    @staticmethod
+    def forward(ctx, a_row, a_col, v, bias, rowptr, col, slope, csc, dropout_p, seed):
+        out, stat = _gat_fw_raw(rowptr, col, a_row, a_col, v, bias, slope, dropout_p, seed)
+        ctx.save_for_backward(a_row, a_col, v, bias, out, stat)
+        ctx.pattern, ctx.slope, ctx.csc = (rowptr, col), slope, csc
+        ctx.dropout_p, ctx.seed = dropout_p, seed  # two Python scalars: the backward recomputes the mask
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        a_row, a_col, v, bias, out, stat = ctx.saved_tensors
+        rowptr, col = ctx.pattern
+        grads = gat_attention_bw(rowptr, col, a_row, a_col, v, bias, ctx.slope, grad, out, stat, ctx.csc,
+                                 ctx.needs_input_grad[:4], ctx.dropout_p, ctx.seed)
+        return grads + (None, None, None, None, None, None)
+
+
+def gat_attention(rowptr: torch.Tensor, col: torch.Tensor, a_row: torch.Tensor, a_col: torch.Tensor, v: torch.Tensor,
+                  bias: Optional[torch.Tensor] = None, negative_slope: float = 0.2, csc=None, dropout_p: float = 0.0,
+                  seed: Optional[int] = None) -> torch.Tensor:
+    """[M, H, F]: the aggregation of a GAT layer in one pass per row.  With a_row [M, H], a_col [N, H] (one scalar
+    per node and head) and v [N, H, F], all float32 or all bfloat16, and bias fp32 [nnz] or [nnz, H]:
+
+        z[e, h]      = (a_row[row(e), h] + a_col[col[e], h]) (+ bias)
+        s[e, h]      = z if z > 0 else negative_slope * z        (z == 0 takes the slope, as leaky_relu's backward)
+        out[r, h, :] = sum over the entries of row r of softmax_row(s)[e, h] * v[col[e], h, :]
+
+    1-D a_row [M], a_col [N] with v [N, F] are one head and give [M, F].  The kernels are those of `attention` with
+    the dot replaced by the sum (psa_gat_attention_fw / _bw_entries and their _half forms): nothing per entry is
+    kept, the backward recomputes the scores from {max, sum} per row and head, grad_a_row and grad_a_col are
+    segment sums of dZ = dS * (1 or negative_slope) over the rows and the columns, grad_v is psa_spmm_heads over
+    the CSC view, grad_bias is dZ.  bfloat16 operands: half-width loads, fp32 arithmetic, each bfloat16 result
+    rounded once; bias and its gradient stay fp32.  Differentiable in a_row, a_col, v and bias; negative_slope is a
+    finite Python float.  A -inf bias masks an entry for negative_slope > 0; with negative_slope == 0 it is
+    0 * -inf = NaN and poisons its row and head.  `csc`, dropout_p and seed as for `attention`: the same mask for
+    the same seed."""
+    rowptr, col, a_row, a_col, v, bias, flat = _gat_operands(rowptr, col, a_row, a_col, v, bias)
+    slope = _slope_arg(negative_slope)
+    dropout_p, seed = _dropout_args(dropout_p, seed, "gat_attention")  # resolved here: forward and backward see one value
+    if needs_grad(a_row) or needs_grad(a_col) or needs_grad(v) or needs_grad(bias):
+        out = _GatAttention.apply(a_row, a_col, v, bias, rowptr, col, slope, csc, dropout_p, seed)
+    else:
+        out = _gat_fw_raw(rowptr, col, a_row, a_col, v, bias, slope, dropout_p, seed)[0]
+    return out[:, 0] if flat else out

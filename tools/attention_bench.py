@@ -40,11 +40,22 @@ ops.attention_dropout_mask, alternating call by call, and print the peak memory 
 with --dtype bf16 the two fused sides take bfloat16 operands (the chain stays fp32).  Dropout moves no extra bytes
 (the mask is recomputed), so the byte model is that of the op without it.
 
-usage: python tools/attention_bench.py [--quick] [--once] [--heads] [--fused [--dtype bf16] [--dropout P]]
+The GAT lines (--gat: H = 8 with F = 16 and 64, H = 1 with F = 64) run SparseTensor.gat_attention beside (a) the
+unfused chain it restates (torch indexing for z = a_row[row] + a_col[col], torch.where for the activation,
+ops.segment_softmax, ops.spmm_heads; fp32) and (b) the dot-product fused op SparseTensor.attention at K = F on the
+same pattern, which moves 4HK more bytes per entry and does the dot: the yardstick of the stage the two share.  The
+three alternate call by call, forward and forward + backward, each with its [min .. max].  Byte model of DESIGN.md
+section 3.13, e the element size: the forward reads nnz*(8 + e*H + e*H*F) + M*e*H and writes M*(e*H*F + 8H).  Under
+each pair the peak memory of one forward + backward of each side.  --dtype bf16 gives the two fused sides bfloat16
+operands, --dropout P gives all three the same dropout (the chain with the materialised mask of
+ops.attention_dropout_mask).
+
+usage: python tools/attention_bench.py [--quick] [--once] [--heads] [--fused | --gat [--dtype bf16] [--dropout P]]
   --quick  config 3 only;  --once  one call of each of our ops and nothing else (for a kernel trace);
-  --heads  the multi-head lines only;  --fused  the fused-attention lines only;
-  --dtype bf16  (with --fused) the bf16 fused op beside the fp32 fused op
-  --dropout P   (with --fused) the fused op with dropout beside the op without and the chain with the same mask"""
+  --heads  the multi-head lines only;  --fused  the fused-attention lines only;  --gat  the GAT lines only;
+  --dtype bf16  (with --fused) the bf16 fused op beside the fp32 fused op; (with --gat) bf16 operands
+  --dropout P   (with --fused) the fused op with dropout beside the op without and the chain with the same mask;
+                (with --gat) dropout P on every side"""
 import statistics
 import sys
 from pathlib import Path
@@ -365,6 +376,84 @@ def run_fused_dropout(N, rowptr, col, gen, once, drop, half):
         torch.cuda.empty_cache()
 
 
+def run_gat(N, rowptr, col, gen, once, half, drop):
+    """gat_attention ("ours" of each line) beside the unfused chain and the dot-product fused op at K = F."""
+    nnz = col.numel()
+    A = SparseTensor(rowptr=rowptr, col=col, sparse_sizes=(N, N), is_sorted=True, trust_data=True)
+    st = A.storage
+    csc = (st.colptr(), st._row_in_csc_order(), st.csr2csc())  # the CSC view of the backward, built once for every side
+    row = None
+    p_drop = 0.0 if drop is None else drop
+    seed, inv_keep = 12345, float(torch.tensor(1.0 / (1.0 - p_drop), dtype=torch.float32))
+    dt = torch.bfloat16 if half else torch.float32
+    e = 2 if half else 4
+    for H, F in ((8, 16), (8, 64), (1, 64)):
+        K = F
+        dense, edge = N * H * F * 4, nnz * H * 4
+        tag = f"H = {H}, F = {F}" + ("" if drop is None else f", dropout {drop}") + (", bf16" if half else "")
+        if not fits(5 * dense + 2 * edge):  # v, the upstream gradient, out, grad_v and a transient; p and dZ
+            print(f"   {tag}: not run, the operands and gradients alone take {5 * dense / 1e9:.0f} GB", flush=True)
+            continue
+        dot_fits = fits(10 * dense + 2 * edge)  # q, k and their gradients on top
+        chain_fits = fits((7 if half else 5) * dense + 10 * edge + nnz * 8)  # z, s, the weights, their gradients, row
+        a_row = (torch.randn((N, H), generator=gen, device=dev)).to(dt)
+        a_col = (torch.randn((N, H), generator=gen, device=dev)).to(dt)
+        v = torch.randn((N, H, F), generator=gen, device=dev).to(dt)
+        go = torch.randn((N, H, F), generator=gen, device=dev).to(dt)
+        if dot_fits:
+            q = (torch.randn((N, H, K), generator=gen, device=dev) * 0.125).to(dt)
+            k = torch.randn((N, H, K), generator=gen, device=dev).to(dt)
+        if chain_fits:
+            if row is None:
+                row = ops.ptr2ind(rowptr, nnz)
+            r32, c32, v32, go32 = ((t.float() for t in (a_row, a_col, v, go)) if half else (a_row, a_col, v, go))
+
+        def forward(kind, rr=None, cc=None, vv=None):
+            if kind == "gat":
+                rr, cc, vv = (a_row, a_col, v) if rr is None else (rr, cc, vv)
+                return A.gat_attention(rr, cc, vv, dropout_p=p_drop, seed=seed)
+            if kind == "dot":  # rr, cc stand for q, k
+                rr, cc, vv = (q, k, v) if rr is None else (rr, cc, vv)
+                return A.attention(rr, cc, vv, dropout_p=p_drop, seed=seed)
+            rr, cc, vv = (r32, c32, v32) if rr is None else (rr, cc, vv)
+            z = rr[row] + cc[col]
+            att = ops.segment_softmax(torch.where(z > 0, z, 0.2 * z), rowptr)
+            if drop is not None:
+                att = att * ops.attention_dropout_mask(nnz, H, p_drop, seed) * inv_keep
+            return ops.spmm_heads(rowptr, col, att, vv, csc=csc)
+
+        def step(kind):
+            def run():
+                src = {"gat": lambda: (a_row, a_col, v), "dot": lambda: (q, k, v), "chain": lambda: (r32, c32, v32)}[kind]()
+                rr, cc, vv = (t.detach().requires_grad_() for t in src)
+                forward(kind, rr, cc, vv).backward(go32 if kind == "chain" else go)
+            return run
+
+        step("gat")()
+        if once:
+            continue
+        if chain_fits:
+            diff = float((forward("gat").float() - forward("chain")).abs().max())
+            print(f"   {tag}: max |gat - chain| = {diff:.2e}", flush=True)
+        model = nnz * (8 + e * H + e * H * F) + N * e * H + N * (e * H * F + 8 * H)
+        heads_line(f"gat forward, {tag}",
+                   [("gat", lambda: forward("gat")), ("chain", (lambda: forward("chain")) if chain_fits else None),
+                    ("dot fused", (lambda: forward("dot")) if dot_fits else None)], model)
+        heads_line(f"gat fwd + bwd, {tag}",
+                   [("gat", step("gat")), ("chain", step("chain") if chain_fits else None),
+                    ("dot fused", step("dot") if dot_fits else None)])
+        peak_c = f"{peak_of(step('chain')):7.3f} GB" if chain_fits else "not run (memory)"
+        peak_d = f"{peak_of(step('dot')):7.3f} GB" if dot_fits else "not run (memory)"
+        print(f"   {'peak memory of one fwd + bwd':34s} gat {peak_of(step('gat')):7.3f} GB   chain {peak_c}   "
+              f"dot fused {peak_d}", flush=True)
+        del a_row, a_col, v, go
+        if dot_fits:
+            del q, k
+        if chain_fits:
+            del r32, c32, v32, go32
+        torch.cuda.empty_cache()
+
+
 def torch_softmax(v, row, M):
     shape = (M,) + tuple(v.shape[1:])
     m = torch.zeros(shape, device=dev).scatter_reduce(0, row.view((-1,) + (1,) * (v.dim() - 1)).expand_as(v), v, "amax",
@@ -399,7 +488,7 @@ def rmat24():
     return N, rowptr, col
 
 
-def run(name, make, once, heads_only=False, fused_only=False, half=False, drop=None):
+def run(name, make, once, heads_only=False, fused_only=False, half=False, drop=None, gat_only=False):
     N, rowptr, col = make()
     nnz = col.numel()
     row = ops.ptr2ind(rowptr, nnz)
@@ -407,6 +496,10 @@ def run(name, make, once, heads_only=False, fused_only=False, half=False, drop=N
     print(f"== {name}: {N} x {N}, {nnz} entries, longest row {int(deg.max())}, "
           f"{int((deg > 128).sum())} rows above 128 entries", flush=True)
     gen = torch.Generator(device=dev).manual_seed(9)
+    if gat_only:
+        del row
+        run_gat(N, rowptr, col, gen, once, half, drop)
+        return
     if fused_only:
         del row
         if drop is not None:
@@ -480,11 +573,14 @@ if __name__ == "__main__":
     once = "--once" in sys.argv
     heads_only = "--heads" in sys.argv
     fused_only = "--fused" in sys.argv
+    gat_only = "--gat" in sys.argv
+    if gat_only and (fused_only or heads_only):
+        sys.exit("--gat goes alone, with --dtype, --dropout, --quick and --once")
     half = False
     if "--dtype" in sys.argv:
         dtype = sys.argv[sys.argv.index("--dtype") + 1:][:1]
-        if dtype not in (["bf16"], ["fp32"]) or not fused_only:
-            sys.exit("--dtype takes bf16 or fp32 and goes with --fused")
+        if dtype not in (["bf16"], ["fp32"]) or not (fused_only or gat_only):
+            sys.exit("--dtype takes bf16 or fp32 and goes with --fused or --gat")
         half = dtype == ["bf16"]
     drop = None
     if "--dropout" in sys.argv:
@@ -493,8 +589,8 @@ if __name__ == "__main__":
             drop = float(arg[0])
         except (IndexError, ValueError):
             drop = -1.0
-        if not 0.0 < drop < 1.0 or not fused_only:
-            sys.exit("--dropout takes a probability in (0, 1) and goes with --fused")
-    run("config-3 shape", config3, once, heads_only, fused_only, half, drop)
+        if not 0.0 < drop < 1.0 or not (fused_only or gat_only):
+            sys.exit("--dropout takes a probability in (0, 1) and goes with --fused or --gat")
+    run("config-3 shape", config3, once, heads_only, fused_only, half, drop, gat_only)
     if "--quick" not in sys.argv:
-        run("R-MAT 24", rmat24, once, heads_only, fused_only, half, drop)
+        run("R-MAT 24", rmat24, once, heads_only, fused_only, half, drop, gat_only)
