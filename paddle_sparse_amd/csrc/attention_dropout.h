@@ -1,4 +1,4 @@
-// Dropout of the attention weights, shared by attention.hip and attention_half.hip.
+// Dropout of the attention weights, shared by both formats of attention_kernels.h.
 //
 //   T          = floor(dropout_p * 2^24)                        (in double; 0 <= T < 2^24)
 //   r(e, h)    = mix64(rand_stream(seed, e) + h)                (rng.h; e = position of the entry in CSR order,

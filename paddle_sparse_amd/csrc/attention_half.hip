@@ -1,1047 +1,10 @@
-// Fused sparse attention with two-byte dense operands (bf16), gfx950: attention.hip's plan with half-width
-// gathers.  q, k, v, out and grad_out are bf16; every product, the scores, the online softmax, {m, l}, the
-// accumulators and the long-row partials are fp32, and a bf16 result is rounded once (nearest even) where it
-// is written.  The bias, stat, p and dS stay fp32.
+// Fused sparse attention with two-byte dense operands (bf16): the entry points over attention_kernels.h (the
+// plan and what bf16 changes in it are there).  dtype: PSA_BF16 is served.
 //
-//   psa_attention_half_fw          out bf16 [M, H, F] = round(acc / l) and stat fp32 [M, H, 2] = {m, l}
-//   psa_attention_half_bw_entries  p and dS = p * (dP - delta) fp32 [nnz, H]; delta = <grad_out, out> is taken
-//                                  from the saved, rounded out
-//   psa_attention_half_dropout_fw / _bw_entries  the same with dropout of the weights (attention_dropout.h):
-//                                  inv_keep is applied in fp32 before the one rounding
-//   psa_gat_attention_half_fw / _bw_entries  the additive scores of a GAT layer (attention.hip: A::kGat) with
-//                                  a_row, a_col, v two-byte: element loads widened exactly, sums, the activation
-//                                  and the softmax fp32; dZ is written where dS was
-//
-// Plan (attention.hip, unchanged): one wave per CSR row, 64-entry tiles, scores through the per-wave LDS tile
-// of 64 x Hb floats, online softmax per lane group, rows above psa::kLongRow entries as 128-entry chunks whose
-// fp32 {m, l, unnormalised partial row} are merged in chunk order.  A lane owns VEC ELEMENTS where it owned
-// VEC floats:
-//   VEC = 8  one 16-byte load of 8 elements (half_util.h: widen8 / narrow8), when K % 8 == 0, F % 8 == 0 and
-//            q, k, v, out (and grad_out) start on 16 bytes;
-//   VEC = 1  2-byte loads (widen1 / narrow1) for every other K, F >= 1 at any 2-byte alignment.
-// There is no 8-byte middle form.  Heads go in blocks of Hb <= 16 with Hb * F elements within the tiles of
-// accumulators a lane keeps: four tiles of 64 elements in the element form, two tiles of 512 in the 16-byte
-// form (a tile is 8 fp32 accumulators per lane there; four of them beside the four slices of q took the
-// chunk kernel to 256 VGPRs and into AGPR copies), so H <= 16 with H * F <= 1024 is one pass as in fp32.
-// The partials are written as floats (two 16-byte stores per lane for VEC = 8).
-//
-// Non-finite values, reproducibility and capture as attention.hip: plain IEEE arithmetic, expf, no float
-// atomics, no host read.  Every address is formed in 64-bit arithmetic.
-#include "common.h"
-#include "attention_dropout.h"
-#include "half_rows.h"
-#include "long_rows.h"
-
-namespace {
-
-using psa_half::BF16;
-using psa_half::clamp_range;
-using psa_half::elem_t;
-using psa_half::load_f32;
-using psa_half::load_vec;
-using psa_half::pow2_at_least;
-using psa_half::store_f32;
-using psa_half::store_vec;
-
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kMaxChunkBlocks = 4096;
-constexpr int kMaxTiles = 4;  // tiles of accumulators / slices of the row of q kept in registers
-constexpr int kMaxTiles16 = 2;  // tiles of accumulators of the forward's 16-byte form
-constexpr int kHeadBlock = 16;  // heads per pass: the LDS tile is 64 entries x kHeadBlock floats per wave
-
-__device__ __forceinline__ float neg_inf() { return -__builtin_inff(); }
-
-// The lanes of a wave hand data to each other through their LDS tile: LDS operations of one wave
-// complete in order, the fences keep the compiler from moving them across.
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// ---- per-head dots of one row against gathered rows (the psa_sddmm_heads layout) ------------------
-
-struct DotGeo {
-  int64_t K;       // elements per head
-  int64_t stride;  // elements per row of the dense operands (H * K)
-  int PK, kshift;  // lanes per head
-  int PH, hshift;  // heads side by side
-  int kiters;      // steps of PK * VEC elements over K
-  int nit;         // head passes * kiters for a full head block
-};
-
-struct Slice {
-  int h;        // head of the slice inside the head block
-  int64_t off;  // h * K + k: first element of it from the block's first head
-  bool act;     // the lane has elements in it
-  bool last;    // the head's dot is complete after it
-};
-
-template <int VEC>
-__device__ __forceinline__ Slice slice_of(const DotGeo g, int Hs, int it, int hs, int jl) {
-  const int hp = it / g.kiters;
-  const int ki = it - hp * g.kiters;
-  const int64_t k = (static_cast<int64_t>(ki) * g.PK + jl) * VEC;
-  Slice sl;
-  sl.h = hp * g.PH + hs;
-  sl.act = sl.h < Hs && k < g.K;
-  sl.off = static_cast<int64_t>(sl.h) * g.K + k;
-  sl.last = ki == g.kiters - 1;
-  return sl;
-}
-
-__device__ __forceinline__ float fold_head(float dot, int PK) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    if (off < PK) dot += __shfl_xor(dot, off);  // wave-uniform
-  }
-  return dot;
-}
-
-// The slices of xrow that the lane meets, widened and kept in registers (NR > 0 and nit <= NR).
-template <typename T, int VEC, int NR>
-__device__ __forceinline__ void load_slices(const elem_t* __restrict__ xrow, const DotGeo g, int Hs, int lane,
-                                            float (&xr)[NR > 0 ? NR : 1][VEC]) {
-  if constexpr (NR > 0) {
-    const int jl = lane & (g.PK - 1);
-    const int hs = (lane >> g.kshift) & (g.PH - 1);
-#pragma unroll
-    for (int it = 0; it < NR; ++it) {
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) xr[it][i] = 0.f;
-      if (it < g.nit) {
-        const Slice sl = slice_of<VEC>(g, Hs, it, hs, jl);
-        if (sl.act) load_vec<T, VEC>(xrow + sl.off, xr[it]);
-      }
-    }
-  }
-}
-
-// tile[idx * ldt + h] = scale * <xrow[h, :], y[c(idx), h, :]> (+ bias[idx * bstride + h * bhstep]) for the
-// n <= 64 entries whose gathered rows lane idx names in c_l and the Hs heads of the block.  xrow, y and
-// bias point at the block's first head (bias also at the tile's first entry).
-template <typename T, int VEC, int NR>
-__device__ __forceinline__ void dots_tile(const elem_t* __restrict__ y, const elem_t* __restrict__ xrow,
-                                          const float (&xr)[NR > 0 ? NR : 1][VEC], const DotGeo g, int Hs,
-                                          int64_t c_l, int n, int lane, float scale, const float* __restrict__ bias,
-                                          int64_t bstride, int bhstep, float* __restrict__ tile, int ldt) {
-  const int jl = lane & (g.PK - 1);
-  const int hs = (lane >> g.kshift) & (g.PH - 1);
-  const int grp = lane >> (g.kshift + g.hshift);
-  const int G = 64 >> (g.kshift + g.hshift);
-  for (int j = 0; j < n; j += G) {
-    const int idx = j + grp;
-    const bool ok = idx < n;
-    const int64_t c = __shfl(static_cast<long long>(c_l), idx & 63);
-    const elem_t* __restrict__ yrow = y + c * g.stride;
-    float dot = 0.f;
-    auto finish = [&](const Slice sl) {
-      dot = fold_head(dot, g.PK);
-      if (ok && jl == 0 && sl.h < Hs) {
-        float sc = __fmul_rn(scale, dot);
-        if (bias) sc = __fadd_rn(sc, bias[static_cast<int64_t>(idx) * bstride + static_cast<int64_t>(sl.h) * bhstep]);
-        tile[idx * ldt + sl.h] = sc;
-      }
-      dot = 0.f;
-    };
-    if constexpr (NR > 0) {
-#pragma unroll
-      for (int it = 0; it < NR; ++it) {
-        if (it < g.nit) {  // wave-uniform
-          const Slice sl = slice_of<VEC>(g, Hs, it, hs, jl);
-          if (ok && sl.act) {
-            float b[VEC];
-            load_vec<T, VEC>(yrow + sl.off, b);
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) dot += b[i] * xr[it][i];
-          }
-          if (sl.last) finish(sl);
-        }
-      }
-    } else {
-      for (int it = 0; it < g.nit; ++it) {
-        const Slice sl = slice_of<VEC>(g, Hs, it, hs, jl);
-        if (ok && sl.act) {
-          float b[VEC], xv[VEC];
-          load_vec<T, VEC>(yrow + sl.off, b);
-          load_vec<T, VEC>(xrow + sl.off, xv);
-#pragma unroll
-          for (int i = 0; i < VEC; ++i) dot += b[i] * xv[i];
-        }
-        if (sl.last) finish(sl);
-      }
-    }
-  }
-}
-
-// ---- additive scores of a GAT layer: stage (a) without a dot ---------------------------------------
-
-// s of z: z itself where z > 0, the rounded product otherwise (z == 0 and a NaN take the slope branch).
-__device__ __forceinline__ float gat_act(float z, float slope) { return z > 0.f ? z : __fmul_rn(slope, z); }
-
-// tile[idx * Hb + h] = s (ACT) or z, with z = (a_row[row, h] + a_col[c(idx), h]) (+ bias) in fp32, for the
-// n <= 64 entries from base on and the Hs heads from hb on; no contraction, so forward and backward agree bit
-// for bit.  Lane t takes (idx, h) = (t / Hs, t % Hs) for t = lane, lane + 64, ...: the mapping of
-// attn_bw_range's consumer loop.  2-byte loads at any element alignment.
-template <class A, typename T, bool ACT>
-__device__ __forceinline__ void gat_tile(const A& a, int64_t row, int64_t hb, int Hs, int64_t c_l, int n,
-                                         int64_t base, int lane, float* __restrict__ tile) {
-  const int total = n * Hs;
-  for (int t0 = 0; t0 < total; t0 += 64) {  // wave-uniform trips: the shuffle reads every lane's c_l
-    const int t = t0 + lane;
-    const bool ok = t < total;
-    const int idx = ok ? t / Hs : 0;
-    const int h = t - idx * Hs;
-    const int64_t c = __shfl(static_cast<long long>(c_l), idx);
-    if (ok) {
-      const int64_t hh = hb + h;
-      float z = __fadd_rn(psa_half::widen1<T>(a.a_row, row * a.H + hh), psa_half::widen1<T>(a.a_col, c * a.H + hh));
-      if (a.bias) z = __fadd_rn(z, a.bias[(base + idx) * a.bias_heads + (a.bias_heads == 1 ? 0 : hh)]);
-      tile[idx * a.Hb + h] = ACT ? gat_act(z, a.slope) : z;
-    }
-  }
-}
-
-// ---- forward --------------------------------------------------------------------------------------
-
-struct FwArgs {
-  const int64_t* rowptr;
-  const int64_t* col;
-  const elem_t* q;
-  const elem_t* k;
-  const elem_t* v;
-  const float* bias;  // NULL: no bias
-  int64_t bias_heads;  // 1 or H
-  float scale;
-  int64_t M, H, K, F, nnz;
-  int Hb;       // heads per block
-  DotGeo dot;   // scores
-  int P, shift;  // lanes per entry in the aggregation
-  int ntiles;   // tiles of P * VEC elements over Hb * F
-  static constexpr bool kDrop = false;
-  static constexpr bool kGat = false;
-};
-
-// The dropout forms of the kernels take their arguments with the mask's parameters behind them; the plain
-// forms never see them (every use sits under if constexpr (A::kDrop)).
-struct FwDropArgs : FwArgs {
-  static constexpr bool kDrop = true;
-  psa::Drop drop;
-};
-
-// The GAT forms: q, k, scale, K and dot are not used (every use sits under if constexpr (!A::kGat)).
-template <bool DROP>
-struct GatFwArgs : FwArgs {
-  static constexpr bool kDrop = DROP;
-  static constexpr bool kGat = true;
-  const elem_t* a_row;  // [M, H]
-  const elem_t* a_col;  // [N, H]
-  float slope;
-  psa::Drop drop;
-};
-
-// {m, l} of two disjoint sets of entries and the factors that bring their sums to the common maximum.
-// Commutative bit for bit (no contraction), so that both partners of an xor step agree.
-__device__ __forceinline__ void merge_factors(float am, float bm, float& m, float& fa, float& fb) {
-  m = fmaxf(am, bm);
-  fa = am == m ? 1.f : expf(am - m);
-  fb = bm == m ? 1.f : expf(bm - m);
-}
-
-__device__ __forceinline__ float merge_sum(float a, float fa, float b, float fb) {
-  return __fadd_rn(__fmul_rn(a, fa), __fmul_rn(b, fb));
-}
-
-// {m, l, acc} of the entries [s, e) of one row for the NT tiles from tile0 on of head block hb, merged over
-// the lane groups: every lane ends with the fp32 state of the elements it owns.
-// Dropout: keeps[h] holds the keep bits of the tile's 64 entries for head h of the block; a dropped entry
-// counts in l and adds an exact 0 * v to acc.
-template <class A, typename T, int VEC, int NR, int NT>
-__device__ __forceinline__ void attn_range(const A& a, int64_t row, int hb, int Hs, int tile0, int64_t s,
-                                           int64_t e, int lane, float* __restrict__ tile,
-                                           unsigned long long* __restrict__ keeps, float (&m)[NT],
-                                           float (&l)[NT], float (&acc)[NT][VEC]) {
-  constexpr int U = kMaxTiles / NT;  // entries in flight per lane
-  const int grp = lane >> a.shift;
-  const int p = lane & (a.P - 1);
-  const int G = 64 >> a.shift;
-  const int64_t Ds = static_cast<int64_t>(Hs) * a.F;
-  const int64_t vstride = a.H * a.F;
-  const elem_t* __restrict__ qrow = nullptr;
-  const elem_t* __restrict__ kb = nullptr;
-  if constexpr (!A::kGat) {
-    qrow = a.q + row * a.dot.stride + static_cast<int64_t>(hb) * a.K;
-    kb = a.k + static_cast<int64_t>(hb) * a.K;
-  }
-  const elem_t* __restrict__ vb = a.v + static_cast<int64_t>(hb) * a.F;
-  const int bhstep = a.bias_heads == 1 ? 0 : 1;
-  const float* __restrict__ biasb = a.bias ? a.bias + (bhstep ? hb : 0) : nullptr;
-  int64_t d[NT];
-  int hd[NT];
-  bool act[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    d[t] = (static_cast<int64_t>(tile0 + t) * a.P + p) * VEC;
-    act[t] = d[t] < Ds;
-    hd[t] = act[t] ? static_cast<int>(d[t] / a.F) : 0;
-    m[t] = neg_inf();
-    l[t] = 0.f;
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) acc[t][i] = 0.f;
-  }
-  float xr[NR > 0 ? NR : 1][VEC];
-  if constexpr (!A::kGat) load_slices<T, VEC, NR>(qrow, a.dot, Hs, lane, xr);
-  for (int64_t base = s; base < e; base += 64) {
-    const int n = (e - base) < 64 ? static_cast<int>(e - base) : 64;
-    int64_t c_l = 0;
-    if (lane < n) c_l = a.col[base + lane];
-    wave_sync();  // the previous tile has been consumed
-    if constexpr (A::kGat) {
-      gat_tile<A, T, true>(a, row, hb, Hs, c_l, n, base, lane, tile);
-    } else {
-      dots_tile<T, VEC, NR>(kb, qrow, xr, a.dot, Hs, c_l, n, lane, a.scale,
-                            biasb ? biasb + base * a.bias_heads : nullptr, a.bias_heads, bhstep, tile, a.Hb);
-    }
-    if constexpr (A::kDrop) {  // one draw per (entry, head): lane i draws for entry base + i, a ballot per head
-      const uint64_t stream = psa::rand_stream(a.drop.seed, base + lane);
-      for (int h = 0; h < Hs; ++h) {
-        const unsigned long long bits = __ballot(psa::keep_of(stream, static_cast<int64_t>(hb) + h, a.drop.T));
-        if (lane == 0) keeps[h] = bits;
-      }
-    }
-    wave_sync();
-    for (int j = 0; j < n; j += G * U) {
-      float b[U][NT][VEC], sc[U][NT];
-      bool ok[U], kept[U][NT];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int idx = j + u * G + grp;
-        ok[u] = idx < n;
-        const int64_t c = __shfl(static_cast<long long>(c_l), idx & 63);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          sc[u][t] = 0.f;
-          kept[u][t] = true;
-#pragma unroll
-          for (int i = 0; i < VEC; ++i) b[u][t][i] = 0.f;
-          if (ok[u] && act[t]) {
-            sc[u][t] = tile[idx * a.Hb + hd[t]];
-            if constexpr (A::kDrop) kept[u][t] = (keeps[hd[t]] >> idx) & 1ull;
-            load_vec<T, VEC>(vb + c * vstride + d[t], b[u][t]);
-          }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          if (ok[u] && act[t]) {
-            const float mn = fmaxf(m[t], sc[u][t]);
-            if (mn != m[t]) {  // a new maximum: bring l and acc to it (exp(-inf) = 0 for the first entry)
-              const float f = expf(m[t] - mn);
-              l[t] *= f;
-#pragma unroll
-              for (int i = 0; i < VEC; ++i) acc[t][i] *= f;
-              m[t] = mn;
-            }
-            // nothing but -inf so far: against 0, so that -inf adds an exact 0 and a NaN stays a NaN
-            const float w = expf(sc[u][t] - (mn == neg_inf() ? 0.f : mn));
-            l[t] += w;
-            const float wk = kept[u][t] ? w : 0.f;
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) acc[t][i] += wk * b[u][t][i];
-          }
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    if (off >= a.P) {  // wave-uniform
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const float om = __shfl_xor(m[t], off), ol = __shfl_xor(l[t], off);
-        float mn, fa, fb;
-        merge_factors(m[t], om, mn, fa, fb);
-        l[t] = merge_sum(l[t], fa, ol, fb);
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) acc[t][i] = merge_sum(acc[t][i], fa, __shfl_xor(acc[t][i], off), fb);
-        m[t] = mn;
-      }
-    }
-  }
-}
-
-// All head blocks and tiles of the range [s, e) of one row into dst[0 .. H * F) and sdst[0 .. 2 * H):
-// the row itself (NORMALISE: dst is elements, round(acc / l)) or a chunk's partial (dst is floats, acc as it is).
-template <class A, typename T, int VEC, int NR, int NT, bool NORMALISE>
-__device__ __forceinline__ void attn_row(const A& a, int64_t row, int64_t s, int64_t e, int lane,
-                                         float* __restrict__ tile, unsigned long long* __restrict__ keeps,
-                                         void* __restrict__ dst, float* __restrict__ sdst) {
-  const int grp = lane >> a.shift;
-  const int p = lane & (a.P - 1);
-  for (int64_t hb = 0; hb < a.H; hb += a.Hb) {
-    const int Hs = a.H - hb < a.Hb ? static_cast<int>(a.H - hb) : a.Hb;
-    const int64_t Ds = static_cast<int64_t>(Hs) * a.F;
-    for (int tile0 = 0; tile0 < a.ntiles; tile0 += NT) {
-      float m[NT], l[NT], acc[NT][VEC];
-      attn_range<A, T, VEC, NR, NT>(a, row, static_cast<int>(hb), Hs, tile0, s, e, lane, tile, keeps, m, l, acc);
-      if (grp == 0) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          const int64_t d = (static_cast<int64_t>(tile0 + t) * a.P + p) * VEC;
-          if (d < Ds) {
-            if constexpr (NORMALISE) {
-#pragma unroll
-              for (int i = 0; i < VEC; ++i) acc[t][i] = acc[t][i] / l[t];
-              if constexpr (A::kDrop) {  // once per output element, after the division
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) acc[t][i] = __fmul_rn(acc[t][i], a.drop.inv_keep);
-              }
-              store_vec<T, VEC>(static_cast<elem_t*>(dst) + hb * a.F + d, acc[t]);
-            } else {
-              store_f32<VEC>(static_cast<float*>(dst) + hb * a.F + d, acc[t]);
-            }
-            if (d % a.F == 0) {  // the first element of a head
-              const int64_t h = hb + d / a.F;
-              sdst[2 * h] = m[t];
-              sdst[2 * h + 1] = l[t];
-            }
-          }
-        }
-      }
-    }
-  }
-}
-
-// The dropout forms keep their keep bits (kHeadBlock x 64 bits per wave) behind the wave's tile.
-template <class A>
-constexpr int tile_floats() { return 64 * kHeadBlock + (A::kDrop ? 2 * kHeadBlock : 0); }
-
-template <class A>
-__device__ __forceinline__ unsigned long long* keeps_of(float* tile) {
-  return reinterpret_cast<unsigned long long*>(tile + 64 * kHeadBlock);  // 4096 bytes in: 8-byte aligned
-}
-
-template <class A, typename T, int VEC, int NR, int NT>
-__global__ void __launch_bounds__(kThreads)
-attn_half_fw_kernel(const A a, elem_t* __restrict__ out, float* __restrict__ stat,
-                    unsigned long long* __restrict__ long_ctr, psa::LongEntry* __restrict__ long_list) {
-  __shared__ float tiles[kWaves][tile_floats<A>()];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * kWaves + wave;
-  if (row >= a.M) return;
-  int64_t s = a.rowptr[row], e = a.rowptr[row + 1];
-  clamp_range(s, e, a.nnz);
-  if (long_list && e - s > psa::kLongRow) {  // wave-uniform: hand the row to chunk waves
-    if (lane == 0) psa::push_long_row(long_ctr, long_list, row, e - s);
-    return;
-  }
-  const int64_t D = a.H * a.F;
-  elem_t* __restrict__ orow = out + row * D;
-  float* __restrict__ srow = stat + row * a.H * 2;
-  if (e <= s) {  // a row without entries: zeros (+0 has the same bits in both formats) and {-inf, 0}
-    for (int64_t dd = lane; dd < D; dd += 64) orow[dd] = 0;
-    for (int64_t h = lane; h < a.H; h += 64) {
-      srow[2 * h] = neg_inf();
-      srow[2 * h + 1] = 0.f;
-    }
-    return;
-  }
-  attn_row<A, T, VEC, NR, NT, true>(a, row, s, e, lane, tiles[wave], keeps_of<A>(tiles[wave]), orow, srow);
-}
-
-// One wave per 128-entry chunk of a listed row: part[c, 0 .. D) unnormalised and pstat[c, h] = {m, l}, fp32.
-template <class A, typename T, int VEC, int NR, int NT>
-__global__ void __launch_bounds__(kThreads)
-attn_half_fw_chunk_kernel(const A a, const unsigned long long* __restrict__ long_ctr,
-                          const psa::LongEntry* __restrict__ long_list, float* __restrict__ part,
-                          float* __restrict__ pstat) {
-  __shared__ float tiles[kWaves][tile_floats<A>()];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const unsigned long long ctr = *long_ctr;
-  const uint32_t total = static_cast<uint32_t>(ctr & 0xffffffffull);
-  const int nrows = static_cast<int>(ctr >> 32);
-  const uint32_t num_waves = gridDim.x * kWaves;
-  const int64_t D = a.H * a.F;
-  for (uint32_t c = blockIdx.x * kWaves + wave; c < total; c += num_waves) {
-    const psa::LongEntry ent = psa::find_long_entry(long_list, nrows, c);
-    int64_t rs = a.rowptr[ent.row], re = a.rowptr[ent.row + 1];
-    clamp_range(rs, re, a.nnz);
-    const int64_t s = rs + static_cast<int64_t>(c - ent.first_chunk) * psa::kLongChunk;
-    const int64_t e = s + psa::kLongChunk < re ? s + psa::kLongChunk : re;
-    attn_row<A, T, VEC, NR, NT, false>(a, ent.row, s, e, lane, tiles[wave], keeps_of<A>(tiles[wave]),
-                                       part + static_cast<int64_t>(c) * D, pstat + static_cast<int64_t>(c) * a.H * 2);
-  }
-}
-
-// One wave per listed row: its chunks' fp32 partials merged in chunk order, whatever order the list was built
-// in, then the one rounding.  An all -inf chunk carries {-inf, 0} and merges as nothing.
-// DROP: inv_keep is applied here, once per output element and before the one rounding, not by the chunks.
-template <typename T, int VEC, bool DROP>
-__global__ void __launch_bounds__(kThreads)
-attn_half_fw_combine_kernel(int64_t H, int64_t F, const unsigned long long* __restrict__ long_ctr,
-                            const psa::LongEntry* __restrict__ long_list, const float* __restrict__ part,
-                            const float* __restrict__ pstat, elem_t* __restrict__ out, float* __restrict__ stat,
-                            float inv_keep) {
-  const int lane = threadIdx.x & 63;
-  const int nrows = static_cast<int>(*long_ctr >> 32);
-  const int num_waves = static_cast<int>(gridDim.x) * kWaves;
-  const int64_t D = H * F;
-  for (int slot = blockIdx.x * kWaves + (threadIdx.x >> 6); slot < nrows; slot += num_waves) {
-    const psa::LongEntry ent = long_list[slot];
-    for (int64_t d = static_cast<int64_t>(lane) * VEC; d < D; d += 64 * VEC) {
-      const int64_t h = d / F;
-      float m = neg_inf(), l = 0.f, acc[VEC];
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
-      for (uint32_t k = 0; k < ent.num_chunks; ++k) {
-        const int64_t c = static_cast<int64_t>(ent.first_chunk + k);
-        const float cm = pstat[(c * H + h) * 2], cl = pstat[(c * H + h) * 2 + 1];
-        float b[VEC];
-        load_f32<VEC>(part + c * D + d, b);
-        float mn, fa, fb;
-        merge_factors(m, cm, mn, fa, fb);
-        l = merge_sum(l, fa, cl, fb);
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) acc[i] = merge_sum(acc[i], fa, b[i], fb);
-        m = mn;
-      }
-#pragma unroll
-      for (int i = 0; i < VEC; ++i) acc[i] = acc[i] / l;
-      if constexpr (DROP) {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) acc[i] = __fmul_rn(acc[i], inv_keep);
-      }
-      store_vec<T, VEC>(out + ent.row * D + d, acc);
-      if (d % F == 0) {
-        stat[(ent.row * H + h) * 2] = m;
-        stat[(ent.row * H + h) * 2 + 1] = l;
-      }
-    }
-  }
-}
-
-// ---- backward, the per-entry half -----------------------------------------------------------------
-
-struct BwArgs {
-  const int64_t* rowptr;
-  const int64_t* col;
-  const elem_t* q;
-  const elem_t* k;
-  const elem_t* v;
-  const float* bias;
-  int64_t bias_heads;
-  float scale;
-  const elem_t* grad_out;
-  const elem_t* out;
-  const float* stat;
-  int64_t M, H, K, F, nnz;
-  int Hb;
-  DotGeo dot;   // scores: over K
-  DotGeo dotf;  // dP and delta: over F
-  float* p;
-  float* ds;
-  static constexpr bool kDrop = false;
-  static constexpr bool kGat = false;
-};
-
-struct BwDropArgs : BwArgs {
-  static constexpr bool kDrop = true;
-  psa::Drop drop;
-};
-
-// The GAT forms: ds receives dZ; q, k, scale, K and dot are not used.
-template <bool DROP>
-struct GatBwArgs : BwArgs {
-  static constexpr bool kDrop = DROP;
-  static constexpr bool kGat = true;
-  const elem_t* a_row;
-  const elem_t* a_col;
-  float slope;
-  psa::Drop drop;
-};
-
-// p and dS of the entries [s, e) of one row.  Dropout, with D = keep * inv_keep recomputed per (entry, head)
-// by the lane that writes it: p * D where p is written, and dS = p * (D * dP - delta).
-// GAT: tile_s receives z (gat_tile, NRK = 0); the consumer applies the activation, so that it has the sign of z
-// for dZ = dS * (z > 0 ? 1 : slope), rounded once more.
-template <class A, typename T, int VEC, int NRK, int NRF>
-__device__ __forceinline__ void attn_bw_range(const A& a, int64_t row, int64_t s, int64_t e, int lane,
-                                              float* __restrict__ tile_s, float* __restrict__ tile_p,
-                                              float* __restrict__ delta) {
-  const int bhstep = a.bias_heads == 1 ? 0 : 1;
-  for (int64_t hb = 0; hb < a.H; hb += a.Hb) {
-    const int Hs = a.H - hb < a.Hb ? static_cast<int>(a.H - hb) : a.Hb;
-    const elem_t* __restrict__ qrow = nullptr;
-    if constexpr (!A::kGat) qrow = a.q + row * a.dot.stride + hb * a.K;
-    const elem_t* __restrict__ grow = a.grad_out + row * a.dotf.stride + hb * a.F;
-    const float* __restrict__ biasb = a.bias ? a.bias + (bhstep ? hb : 0) : nullptr;
-    float xq[NRK > 0 ? NRK : 1][VEC], xg[NRF > 0 ? NRF : 1][VEC];
-    if constexpr (!A::kGat) load_slices<T, VEC, NRK>(qrow, a.dot, Hs, lane, xq);
-    load_slices<T, VEC, NRF>(grow, a.dotf, Hs, lane, xg);
-    wave_sync();  // the previous head block has been consumed
-    // delta[h] = <grad_out[row, h, :], out[row, h, :]>: the row of the saved (rounded) out as the one gathered row
-    dots_tile<T, VEC, NRF>(a.out + hb * a.F, grow, xg, a.dotf, Hs, row, 1, lane, 1.f, nullptr, 0, 0, delta, 0);
-    for (int64_t base = s; base < e; base += 64) {
-      const int n = (e - base) < 64 ? static_cast<int>(e - base) : 64;
-      int64_t c_l = 0;
-      if (lane < n) c_l = a.col[base + lane];
-      if constexpr (A::kGat) {
-        gat_tile<A, T, false>(a, row, hb, Hs, c_l, n, base, lane, tile_s);
-      } else {
-        dots_tile<T, VEC, NRK>(a.k + hb * a.K, qrow, xq, a.dot, Hs, c_l, n, lane, a.scale,
-                               biasb ? biasb + base * a.bias_heads : nullptr, a.bias_heads, bhstep, tile_s, a.Hb);
-      }
-      dots_tile<T, VEC, NRF>(a.v + hb * a.F, grow, xg, a.dotf, Hs, c_l, n, lane, 1.f, nullptr, 0, 0, tile_p, a.Hb);
-      wave_sync();
-      for (int t = lane; t < n * Hs; t += 64) {
-        const int idx = t / Hs;
-        const int h = t - idx * Hs;
-        const float m = a.stat[(row * a.H + hb + h) * 2], l = a.stat[(row * a.H + hb + h) * 2 + 1];
-        float sc = tile_s[idx * a.Hb + h], fac = 1.f;
-        if constexpr (A::kGat) {
-          fac = sc > 0.f ? 1.f : a.slope;
-          sc = gat_act(sc, a.slope);
-        }
-        const float pe = expf(sc - m) / l;
-        const int64_t at = (base + idx) * a.H + hb + h;
-        float dse;
-        if constexpr (A::kDrop) {
-          const bool kept = psa::keep_of(psa::rand_stream(a.drop.seed, base + idx), hb + h, a.drop.T);
-          const float dk = kept ? a.drop.inv_keep : 0.f;
-          a.p[at] = __fmul_rn(pe, dk);
-          dse = pe * (__fmul_rn(dk, tile_p[idx * a.Hb + h]) - delta[h]);
-        } else {
-          a.p[at] = pe;
-          dse = pe * (tile_p[idx * a.Hb + h] - delta[h]);
-        }
-        a.ds[at] = A::kGat ? __fmul_rn(dse, fac) : dse;
-      }
-      wave_sync();  // before the next tile overwrites
-    }
-  }
-}
-
-template <class A, typename T, int VEC, int NRK, int NRF>
-__global__ void __launch_bounds__(kThreads)
-attn_half_bw_kernel(const A a, unsigned long long* __restrict__ long_ctr,
-                    psa::LongEntry* __restrict__ long_list) {
-  __shared__ float tiles[kWaves][2][64 * kHeadBlock];
-  __shared__ float deltas[kWaves][kHeadBlock];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int64_t row = static_cast<int64_t>(blockIdx.x) * kWaves + wave;
-  if (row >= a.M) return;
-  int64_t s = a.rowptr[row], e = a.rowptr[row + 1];
-  clamp_range(s, e, a.nnz);
-  if (e <= s) return;  // a row without entries writes nothing
-  if (long_list && e - s > psa::kLongRow) {  // wave-uniform: hand the row to chunk waves
-    if (lane == 0) psa::push_long_row(long_ctr, long_list, row, e - s);
-    return;
-  }
-  attn_bw_range<A, T, VEC, NRK, NRF>(a, row, s, e, lane, tiles[wave][0], tiles[wave][1], deltas[wave]);
-}
-
-// One wave per 128-entry chunk of a listed row; chunks write disjoint entries.
-template <class A, typename T, int VEC, int NRK, int NRF>
-__global__ void __launch_bounds__(kThreads)
-attn_half_bw_chunk_kernel(const A a, const unsigned long long* __restrict__ long_ctr,
-                          const psa::LongEntry* __restrict__ long_list) {
-  __shared__ float tiles[kWaves][2][64 * kHeadBlock];
-  __shared__ float deltas[kWaves][kHeadBlock];
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const unsigned long long ctr = *long_ctr;
-  const uint32_t total = static_cast<uint32_t>(ctr & 0xffffffffull);
-  const int nrows = static_cast<int>(ctr >> 32);
-  const uint32_t num_waves = gridDim.x * kWaves;
-  for (uint32_t c = blockIdx.x * kWaves + wave; c < total; c += num_waves) {
-    const psa::LongEntry ent = psa::find_long_entry(long_list, nrows, c);
-    int64_t rs = a.rowptr[ent.row], re = a.rowptr[ent.row + 1];
-    clamp_range(rs, re, a.nnz);
-    const int64_t s = rs + static_cast<int64_t>(c - ent.first_chunk) * psa::kLongChunk;
-    const int64_t e = s + psa::kLongChunk < re ? s + psa::kLongChunk : re;
-    attn_bw_range<A, T, VEC, NRK, NRF>(a, ent.row, s, e, lane, tiles[wave][0], tiles[wave][1], deltas[wave]);
-  }
-}
-
-// ---- host -----------------------------------------------------------------------------------------
-
-// Tiles of accumulators of the forward: kMaxTiles of one element, kMaxTiles16 of eight.
-int fw_tiles(int vec) { return vec == 8 ? kMaxTiles16 : kMaxTiles; }
-
-// Heads per pass: at most kHeadBlock, and Hb * F elements within fw_tiles(vec) tiles of 64 * vec elements.
-int head_block(int64_t H, int64_t F, int vec) {
-  int64_t hb = (static_cast<int64_t>(fw_tiles(vec)) * 64 * vec) / F;
-  hb = hb < 1 ? 1 : hb;
-  hb = hb > kHeadBlock ? kHeadBlock : hb;
-  return static_cast<int>(hb > H ? H : hb);
-}
-
-DotGeo dot_geo(int64_t H, int Hb, int64_t K, int vec) {
-  DotGeo g;
-  g.K = K;
-  g.stride = H * K;
-  const int64_t q = psa::ceil_div(K, vec);
-  g.PK = pow2_at_least(q, 64, &g.kshift);
-  g.PH = pow2_at_least(Hb, 64 / g.PK, &g.hshift);
-  g.kiters = static_cast<int>(psa::ceil_div(q, g.PK));
-  g.nit = static_cast<int>(psa::ceil_div(Hb, g.PH)) * g.kiters;
-  return g;
-}
-
-// The partials are fp32 whatever the operands are: the workspace is psa_attention_workspace_bytes(nnz, H, F).
-size_t part_bytes(int64_t nnz, int64_t D) {
-  return psa::align256(sizeof(float) * static_cast<size_t>(psa::max_long_chunks(nnz)) * static_cast<size_t>(D));
-}
-
-// The long-row list at the head of the workspace, its counter zeroed: 0 rows listed so far.
-int take_list(const char* who, void* workspace, size_t have, size_t need, hipStream_t s, unsigned long long** ctr,
-              psa::LongEntry** list) {
-  if (workspace == nullptr || have < need) {
-    psa::set_error(std::string(who) + ": workspace too small");
-    return PSA_ERR_WORKSPACE;
-  }
-  if (!psa::aligned(workspace, 16)) {
-    psa::set_error(std::string(who) + ": workspace must be 16-byte aligned");
-    return PSA_ERR_INVALID_ARG;
-  }
-  *ctr = static_cast<unsigned long long*>(workspace);
-  *list = reinterpret_cast<psa::LongEntry*>(static_cast<char*>(workspace) + 256);
-  PSA_ZERO(*ctr, 8, s);
-  return PSA_OK;
-}
-
-int chunk_blocks(int64_t n) {
-  const int64_t b = psa::ceil_div(n, kWaves);
-  return static_cast<int>(b > kMaxChunkBlocks ? kMaxChunkBlocks : b);
-}
-
-template <class A, typename T, int VEC, int NR, int NT>
-int launch_fw(const A& a, elem_t* out, float* stat, unsigned long long* ctr, psa::LongEntry* list, float* part,
-              float* pstat, hipStream_t s) {
-  const int64_t gx = psa::ceil_div(a.M, kWaves);
-  PSA_REQUIRE(gx <= 0x7fffffff, "M too large for one launch");
-  hipLaunchKernelGGL((attn_half_fw_kernel<A, T, VEC, NR, NT>), dim3(static_cast<unsigned>(gx)), dim3(kThreads), 0, s, a,
-                     out, stat, ctr, list);
-  if (list) {
-    hipLaunchKernelGGL((attn_half_fw_chunk_kernel<A, T, VEC, NR, NT>), dim3(chunk_blocks(psa::max_long_chunks(a.nnz))),
-                       dim3(kThreads), 0, s, a, ctr, list, part, pstat);
-    float inv_keep = 1.f;
-    if constexpr (A::kDrop) inv_keep = a.drop.inv_keep;
-    hipLaunchKernelGGL((attn_half_fw_combine_kernel<T, VEC, A::kDrop>), dim3(chunk_blocks(psa::max_long_rows(a.nnz))),
-                       dim3(kThreads), 0, s, a.H, a.F, ctr, list, part, pstat, out, stat, inv_keep);
-  }
-  PSA_LAUNCH_CHECK();
-  return PSA_OK;
-}
-
-template <class A, typename T, int VEC, int NRK, int NRF>
-int launch_bw(const A& a, unsigned long long* ctr, psa::LongEntry* list, hipStream_t s) {
-  const int64_t gx = psa::ceil_div(a.M, kWaves);
-  PSA_REQUIRE(gx <= 0x7fffffff, "M too large for one launch");
-  hipLaunchKernelGGL((attn_half_bw_kernel<A, T, VEC, NRK, NRF>), dim3(static_cast<unsigned>(gx)), dim3(kThreads), 0, s,
-                     a, ctr, list);
-  if (list) {
-    hipLaunchKernelGGL((attn_half_bw_chunk_kernel<A, T, VEC, NRK, NRF>), dim3(chunk_blocks(psa::max_long_chunks(a.nnz))),
-                       dim3(kThreads), 0, s, a, ctr, list);
-  }
-  PSA_LAUNCH_CHECK();
-  return PSA_OK;
-}
-
-inline const elem_t* elems(const void* p) { return static_cast<const elem_t*>(p); }
-
-// The entry points share their bodies with their dropout forms; errors carry the caller's name.
-#define ATTN_REQUIRE(cond, msg)                          \
-  do {                                                   \
-    if (!(cond)) {                                       \
-      psa::set_error(std::string(who) + ": " + (msg));   \
-      return PSA_ERR_INVALID_ARG;                        \
-    }                                                    \
-  } while (0)
-
-template <class A>
-int attention_fw(const char* who, const psa::Drop& drop, int dtype, const int64_t* rowptr, const int64_t* col,
-                 const void* q, const void* k, const void* v, const float* bias, int64_t bias_heads, float scale,
-                 int64_t M, int64_t N, int64_t H, int64_t K, int64_t F, int64_t nnz, void* out, float* stat,
-                 void* workspace, size_t workspace_bytes, psa_stream_t stream) {
-  ATTN_REQUIRE(dtype == PSA_BF16, "dtype must be PSA_BF16");
-  ATTN_REQUIRE(M >= 0 && N >= 0 && nnz >= 0, "negative size");
-  ATTN_REQUIRE(H >= 1 && K >= 1 && F >= 1, "H, K and F must be at least 1");
-  ATTN_REQUIRE(nnz < (int64_t{1} << 38), "nnz too large");
-  ATTN_REQUIRE(H < (int64_t{1} << 24) && K < (int64_t{1} << 24) && F < (int64_t{1} << 24), "H, K or F too large");
-  ATTN_REQUIRE(bias == nullptr || bias_heads == 1 || bias_heads == H, "bias_heads must be 1 or H");
-  if (M == 0) return PSA_OK;
-  ATTN_REQUIRE(rowptr && out && stat, "NULL pointer");
-  ATTN_REQUIRE(nnz == 0 || (col && q && k && v), "NULL pointer");
-  ATTN_REQUIRE(psa::aligned(q, 2) && psa::aligned(k, 2) && psa::aligned(v, 2) && psa::aligned(out, 2),
-              "operands must be 2-byte aligned");
-  hipStream_t s = psa::as_stream(stream);
-  unsigned long long* ctr = nullptr;
-  psa::LongEntry* list = nullptr;
-  float *part = nullptr, *pstat = nullptr;
-  if (nnz > psa::kLongRow) {
-    const int rc = take_list(who, workspace, workspace_bytes,
-                             psa_attention_workspace_bytes(nnz, H, F), s, &ctr, &list);
-    if (rc != PSA_OK) return rc;
-    char* w = static_cast<char*>(workspace) + psa::long_list_bytes(nnz);
-    part = reinterpret_cast<float*>(w);
-    pstat = reinterpret_cast<float*>(w + part_bytes(nnz, H * F));
-  }
-  const bool v8 = (K % 8 == 0) && (F % 8 == 0) && psa::aligned(q, 16) && psa::aligned(k, 16) && psa::aligned(v, 16) &&
-                  psa::aligned(out, 16);
-  const int vec = v8 ? 8 : 1;
-  A a;
-  if constexpr (A::kDrop) a.drop = drop;
-  a.rowptr = rowptr;
-  a.col = col;
-  a.q = elems(q);
-  a.k = elems(k);
-  a.v = elems(v);
-  a.bias = bias;
-  a.bias_heads = bias ? bias_heads : 1;
-  a.scale = scale;
-  a.M = M;
-  a.H = H;
-  a.K = K;
-  a.F = F;
-  a.nnz = nnz;
-  a.Hb = head_block(H, F, vec);
-  a.dot = dot_geo(H, a.Hb, K, vec);
-  const int64_t Db = static_cast<int64_t>(a.Hb) * F;
-  a.P = pow2_at_least(psa::ceil_div(Db, vec), 64, &a.shift);
-  const int64_t ntiles = psa::ceil_div(Db, static_cast<int64_t>(a.P) * vec);
-  a.ntiles = static_cast<int>(ntiles);
-  const bool regs = a.dot.nit <= kMaxTiles;
-  elem_t* o = static_cast<elem_t*>(out);
-#define PSA_ATTN_FW(VEC, NR, NT) return launch_fw<A, BF16, VEC, NR, NT>(a, o, stat, ctr, list, part, pstat, s)
-#define PSA_ATTN_FW_NT(VEC, NR)         \
-  do {                                  \
-    if (ntiles == 1) PSA_ATTN_FW(VEC, NR, 1); \
-    if (ntiles == 2) PSA_ATTN_FW(VEC, NR, 2); \
-    PSA_ATTN_FW(VEC, NR, 4);            \
-  } while (0)
-  if (v8) {  // one or two tiles per pass; a wider head block repeats the pass per pair of tiles
-    if (regs) {
-      if (ntiles == 1) PSA_ATTN_FW(8, 4, 1);
-      PSA_ATTN_FW(8, 4, 2);
-    }
-    if (ntiles == 1) PSA_ATTN_FW(8, 0, 1);
-    PSA_ATTN_FW(8, 0, 2);
-  }
-  if (regs) PSA_ATTN_FW_NT(1, 4);
-  PSA_ATTN_FW_NT(1, 0);
-#undef PSA_ATTN_FW_NT
-#undef PSA_ATTN_FW
-}
-
-template <class A>
-int attention_bw(const char* who, const psa::Drop& drop, int dtype, const int64_t* rowptr, const int64_t* col,
-                 const void* q, const void* k, const void* v, const float* bias, int64_t bias_heads, float scale,
-                 const void* grad_out, const void* out, const float* stat, int64_t M, int64_t N, int64_t H,
-                 int64_t K, int64_t F, int64_t nnz, float* p, float* ds, void* workspace, size_t workspace_bytes,
-                 psa_stream_t stream) {
-  ATTN_REQUIRE(dtype == PSA_BF16, "dtype must be PSA_BF16");
-  ATTN_REQUIRE(M >= 0 && N >= 0 && nnz >= 0, "negative size");
-  ATTN_REQUIRE(H >= 1 && K >= 1 && F >= 1, "H, K and F must be at least 1");
-  ATTN_REQUIRE(nnz < (int64_t{1} << 38), "nnz too large");
-  ATTN_REQUIRE(H < (int64_t{1} << 24) && K < (int64_t{1} << 24) && F < (int64_t{1} << 24), "H, K or F too large");
-  ATTN_REQUIRE(bias == nullptr || bias_heads == 1 || bias_heads == H, "bias_heads must be 1 or H");
-  if (M == 0 || nnz == 0) return PSA_OK;
-  ATTN_REQUIRE(rowptr && col && q && k && v && grad_out && out && stat && p && ds, "NULL pointer");
-  ATTN_REQUIRE(psa::aligned(q, 2) && psa::aligned(k, 2) && psa::aligned(v, 2) && psa::aligned(grad_out, 2) &&
-                  psa::aligned(out, 2),
-              "operands must be 2-byte aligned");
-  hipStream_t s = psa::as_stream(stream);
-  unsigned long long* ctr = nullptr;
-  psa::LongEntry* list = nullptr;
-  if (nnz > psa::kLongRow) {
-    const int rc = take_list(who, workspace, workspace_bytes, psa::long_list_bytes(nnz), s, &ctr, &list);
-    if (rc != PSA_OK) return rc;
-  }
-  const bool v8 = (K % 8 == 0) && (F % 8 == 0) && psa::aligned(q, 16) && psa::aligned(k, 16) && psa::aligned(v, 16) &&
-                  psa::aligned(grad_out, 16) && psa::aligned(out, 16);
-  const int vec = v8 ? 8 : 1;
-  A a;
-  if constexpr (A::kDrop) a.drop = drop;
-  a.rowptr = rowptr;
-  a.col = col;
-  a.q = elems(q);
-  a.k = elems(k);
-  a.v = elems(v);
-  a.bias = bias;
-  a.bias_heads = bias ? bias_heads : 1;
-  a.scale = scale;
-  a.grad_out = elems(grad_out);
-  a.out = elems(out);
-  a.stat = stat;
-  a.M = M;
-  a.H = H;
-  a.K = K;
-  a.F = F;
-  a.nnz = nnz;
-  a.Hb = static_cast<int>(H < kHeadBlock ? H : kHeadBlock);
-  a.dot = dot_geo(H, a.Hb, K, vec);
-  a.dotf = dot_geo(H, a.Hb, F, vec);
-  a.p = p;
-  a.ds = ds;
-  const bool rk = a.dot.nit <= kMaxTiles, rf = a.dotf.nit <= kMaxTiles;
-#define PSA_ATTN_BW(VEC, NRK, NRF) return launch_bw<A, BF16, VEC, NRK, NRF>(a, ctr, list, s)
-#define PSA_ATTN_BW_NR(VEC)           \
-  do {                                \
-    if (rk && rf) PSA_ATTN_BW(VEC, 4, 4); \
-    if (rk) PSA_ATTN_BW(VEC, 4, 0);   \
-    if (rf) PSA_ATTN_BW(VEC, 0, 4);   \
-    PSA_ATTN_BW(VEC, 0, 0);           \
-  } while (0)
-  if (v8) PSA_ATTN_BW_NR(8);
-  PSA_ATTN_BW_NR(1);
-#undef PSA_ATTN_BW_NR
-#undef PSA_ATTN_BW
-}
-
-// ---- GAT: the same launches without the slices of q (NR = NRK = 0) --------------------------------
-
-// Everything of the argument struct that the dot-product scores alone use.
-template <class A>
-void gat_no_dot(A* a) {
-  a->q = nullptr;
-  a->k = nullptr;
-  a->scale = 1.f;
-  a->K = 1;
-  a->dot = DotGeo{};
-}
-
-template <bool DROP>
-int gat_fw(const char* who, const psa::Drop& drop, int dtype, const int64_t* rowptr, const int64_t* col,
-           const void* a_row, const void* a_col, const void* v, const float* bias, int64_t bias_heads, float slope,
-           int64_t M, int64_t N, int64_t H, int64_t F, int64_t nnz, void* out, float* stat, void* workspace,
-           size_t workspace_bytes, psa_stream_t stream) {
-  using A = GatFwArgs<DROP>;
-  ATTN_REQUIRE(dtype == PSA_BF16, "dtype must be PSA_BF16");
-  ATTN_REQUIRE(M >= 0 && N >= 0 && nnz >= 0, "negative size");
-  ATTN_REQUIRE(H >= 1 && F >= 1, "H and F must be at least 1");
-  ATTN_REQUIRE(nnz < (int64_t{1} << 38), "nnz too large");
-  ATTN_REQUIRE(H < (int64_t{1} << 24) && F < (int64_t{1} << 24), "H or F too large");
-  ATTN_REQUIRE(bias == nullptr || bias_heads == 1 || bias_heads == H, "bias_heads must be 1 or H");
-  ATTN_REQUIRE(std::isfinite(slope), "negative_slope must be finite");
-  if (M == 0) return PSA_OK;
-  ATTN_REQUIRE(rowptr && out && stat, "NULL pointer");
-  ATTN_REQUIRE(nnz == 0 || (col && a_row && a_col && v), "NULL pointer");
-  ATTN_REQUIRE(psa::aligned(a_row, 2) && psa::aligned(a_col, 2) && psa::aligned(v, 2) && psa::aligned(out, 2),
-              "operands must be 2-byte aligned");
-  hipStream_t s = psa::as_stream(stream);
-  unsigned long long* ctr = nullptr;
-  psa::LongEntry* list = nullptr;
-  float *part = nullptr, *pstat = nullptr;
-  if (nnz > psa::kLongRow) {
-    const int rc = take_list(who, workspace, workspace_bytes,
-                             psa_attention_workspace_bytes(nnz, H, F), s, &ctr, &list);
-    if (rc != PSA_OK) return rc;
-    char* w = static_cast<char*>(workspace) + psa::long_list_bytes(nnz);
-    part = reinterpret_cast<float*>(w);
-    pstat = reinterpret_cast<float*>(w + part_bytes(nnz, H * F));
-  }
-  const bool v8 = (F % 8 == 0) && psa::aligned(v, 16) && psa::aligned(out, 16);
-  const int vec = v8 ? 8 : 1;
-  A a;
-  gat_no_dot(&a);
-  a.drop = drop;
-  a.rowptr = rowptr;
-  a.col = col;
-  a.a_row = elems(a_row);
-  a.a_col = elems(a_col);
-  a.slope = slope;
-  a.v = elems(v);
-  a.bias = bias;
-  a.bias_heads = bias ? bias_heads : 1;
-  a.M = M;
-  a.H = H;
-  a.F = F;
-  a.nnz = nnz;
-  a.Hb = head_block(H, F, vec);
-  const int64_t Db = static_cast<int64_t>(a.Hb) * F;
-  a.P = pow2_at_least(psa::ceil_div(Db, vec), 64, &a.shift);
-  const int64_t ntiles = psa::ceil_div(Db, static_cast<int64_t>(a.P) * vec);
-  a.ntiles = static_cast<int>(ntiles);
-  elem_t* o = static_cast<elem_t*>(out);
-#define PSA_GAT_FW(VEC, NT) return launch_fw<A, BF16, VEC, 0, NT>(a, o, stat, ctr, list, part, pstat, s)
-  if (v8) {
-    if (ntiles == 1) PSA_GAT_FW(8, 1);
-    PSA_GAT_FW(8, 2);
-  }
-  if (ntiles == 1) PSA_GAT_FW(1, 1);
-  if (ntiles == 2) PSA_GAT_FW(1, 2);
-  PSA_GAT_FW(1, 4);
-#undef PSA_GAT_FW
-}
-
-template <bool DROP>
-int gat_bw(const char* who, const psa::Drop& drop, int dtype, const int64_t* rowptr, const int64_t* col,
-           const void* a_row, const void* a_col, const void* v, const float* bias, int64_t bias_heads, float slope,
-           const void* grad_out, const void* out, const float* stat, int64_t M, int64_t N, int64_t H, int64_t F,
-           int64_t nnz, float* p, float* dz, void* workspace, size_t workspace_bytes, psa_stream_t stream) {
-  using A = GatBwArgs<DROP>;
-  ATTN_REQUIRE(dtype == PSA_BF16, "dtype must be PSA_BF16");
-  ATTN_REQUIRE(M >= 0 && N >= 0 && nnz >= 0, "negative size");
-  ATTN_REQUIRE(H >= 1 && F >= 1, "H and F must be at least 1");
-  ATTN_REQUIRE(nnz < (int64_t{1} << 38), "nnz too large");
-  ATTN_REQUIRE(H < (int64_t{1} << 24) && F < (int64_t{1} << 24), "H or F too large");
-  ATTN_REQUIRE(bias == nullptr || bias_heads == 1 || bias_heads == H, "bias_heads must be 1 or H");
-  ATTN_REQUIRE(std::isfinite(slope), "negative_slope must be finite");
-  if (M == 0 || nnz == 0) return PSA_OK;
-  ATTN_REQUIRE(rowptr && col && a_row && a_col && v && grad_out && out && stat && p && dz, "NULL pointer");
-  ATTN_REQUIRE(psa::aligned(a_row, 2) && psa::aligned(a_col, 2) && psa::aligned(v, 2) && psa::aligned(grad_out, 2) &&
-                  psa::aligned(out, 2),
-              "operands must be 2-byte aligned");
-  hipStream_t s = psa::as_stream(stream);
-  unsigned long long* ctr = nullptr;
-  psa::LongEntry* list = nullptr;
-  if (nnz > psa::kLongRow) {
-    const int rc = take_list(who, workspace, workspace_bytes, psa::long_list_bytes(nnz), s, &ctr, &list);
-    if (rc != PSA_OK) return rc;
-  }
-  const bool v8 = (F % 8 == 0) && psa::aligned(v, 16) && psa::aligned(grad_out, 16) && psa::aligned(out, 16);
-  const int vec = v8 ? 8 : 1;
-  A a;
-  gat_no_dot(&a);
-  a.drop = drop;
-  a.rowptr = rowptr;
-  a.col = col;
-  a.a_row = elems(a_row);
-  a.a_col = elems(a_col);
-  a.slope = slope;
-  a.v = elems(v);
-  a.bias = bias;
-  a.bias_heads = bias ? bias_heads : 1;
-  a.grad_out = elems(grad_out);
-  a.out = elems(out);
-  a.stat = stat;
-  a.M = M;
-  a.H = H;
-  a.F = F;
-  a.nnz = nnz;
-  a.Hb = static_cast<int>(H < kHeadBlock ? H : kHeadBlock);
-  a.dotf = dot_geo(H, a.Hb, F, vec);
-  a.p = p;
-  a.ds = dz;
-  const bool rf = a.dotf.nit <= kMaxTiles;
-  if (v8) {
-    if (rf) return launch_bw<A, BF16, 8, 0, 4>(a, ctr, list, s);
-    return launch_bw<A, BF16, 8, 0, 0>(a, ctr, list, s);
-  }
-  if (rf) return launch_bw<A, BF16, 1, 0, 4>(a, ctr, list, s);
-  return launch_bw<A, BF16, 1, 0, 0>(a, ctr, list, s);
-}
-
-#undef ATTN_REQUIRE
-
-}  // namespace
+//   psa_attention_half_fw / _bw_entries             attention_fw / attention_bw
+//   psa_attention_half_dropout_fw / _bw_entries     the same with the mask (A::kDrop)
+//   psa_gat_attention_half_fw / _bw_entries         gat_fw / gat_bw (A::kGat)
+#include "attention_kernels.h"
 
 extern "C" {
 
@@ -1049,8 +12,8 @@ int psa_attention_half_fw(int dtype, const int64_t* rowptr, const int64_t* col, 
                           const void* v, const float* bias, int64_t bias_heads, float scale, int64_t M, int64_t N,
                           int64_t H, int64_t K, int64_t F, int64_t nnz, void* out, float* stat, void* workspace,
                           size_t workspace_bytes, psa_stream_t stream) {
-  return attention_fw<FwArgs>("psa_attention_half_fw", psa::Drop{}, dtype, rowptr, col, q, k, v, bias, bias_heads, scale,
-                              M, N, H, K, F, nnz, out, stat, workspace, workspace_bytes, stream);
+  return attention_fw<FwArgs<Bf16>>("psa_attention_half_fw", psa::Drop{}, dtype, rowptr, col, q, k, v, bias, bias_heads,
+                                    scale, M, N, H, K, F, nnz, out, stat, workspace, workspace_bytes, stream);
 }
 
 int psa_attention_half_bw_entries(int dtype, const int64_t* rowptr, const int64_t* col, const void* q, const void* k,
@@ -1058,9 +21,9 @@ int psa_attention_half_bw_entries(int dtype, const int64_t* rowptr, const int64_
                                   const void* grad_out, const void* out, const float* stat, int64_t M, int64_t N,
                                   int64_t H, int64_t K, int64_t F, int64_t nnz, float* p, float* ds, void* workspace,
                                   size_t workspace_bytes, psa_stream_t stream) {
-  return attention_bw<BwArgs>("psa_attention_half_bw_entries", psa::Drop{}, dtype, rowptr, col, q, k, v, bias,
-                              bias_heads, scale, grad_out, out, stat, M, N, H, K, F, nnz, p, ds, workspace,
-                              workspace_bytes, stream);
+  return attention_bw<BwArgs<Bf16>>("psa_attention_half_bw_entries", psa::Drop{}, dtype, rowptr, col, q, k, v, bias,
+                                    bias_heads, scale, grad_out, out, stat, M, N, H, K, F, nnz, p, ds, workspace,
+                                    workspace_bytes, stream);
 }
 
 int psa_attention_half_dropout_fw(int dtype, const int64_t* rowptr, const int64_t* col, const void* q, const void* k,
@@ -1070,8 +33,9 @@ int psa_attention_half_dropout_fw(int dtype, const int64_t* rowptr, const int64_
                                   psa_stream_t stream) {
   psa::Drop drop;
   if (!psa::make_drop("psa_attention_half_dropout_fw", dropout_p, seed, &drop)) return PSA_ERR_INVALID_ARG;
-  return attention_fw<FwDropArgs>("psa_attention_half_dropout_fw", drop, dtype, rowptr, col, q, k, v, bias, bias_heads,
-                                  scale, M, N, H, K, F, nnz, out, stat, workspace, workspace_bytes, stream);
+  return attention_fw<FwDropArgs<Bf16>>("psa_attention_half_dropout_fw", drop, dtype, rowptr, col, q, k, v, bias,
+                                        bias_heads, scale, M, N, H, K, F, nnz, out, stat, workspace, workspace_bytes,
+                                        stream);
 }
 
 int psa_attention_half_dropout_bw_entries(int dtype, const int64_t* rowptr, const int64_t* col, const void* q,
@@ -1082,9 +46,9 @@ int psa_attention_half_dropout_bw_entries(int dtype, const int64_t* rowptr, cons
                                           size_t workspace_bytes, psa_stream_t stream) {
   psa::Drop drop;
   if (!psa::make_drop("psa_attention_half_dropout_bw_entries", dropout_p, seed, &drop)) return PSA_ERR_INVALID_ARG;
-  return attention_bw<BwDropArgs>("psa_attention_half_dropout_bw_entries", drop, dtype, rowptr, col, q, k, v, bias,
-                                  bias_heads, scale, grad_out, out, stat, M, N, H, K, F, nnz, p, ds, workspace,
-                                  workspace_bytes, stream);
+  return attention_bw<BwDropArgs<Bf16>>("psa_attention_half_dropout_bw_entries", drop, dtype, rowptr, col, q, k, v,
+                                        bias, bias_heads, scale, grad_out, out, stat, M, N, H, K, F, nnz, p, ds,
+                                        workspace, workspace_bytes, stream);
 }
 
 // dropout_p == 0 takes the maskless instantiations: the same bits (every entry kept, times 1) without the draws.
@@ -1096,11 +60,11 @@ int psa_gat_attention_half_fw(int dtype, const int64_t* rowptr, const int64_t* c
   psa::Drop drop;
   if (!psa::make_drop("psa_gat_attention_half_fw", dropout_p, seed, &drop)) return PSA_ERR_INVALID_ARG;
   if (dropout_p == 0.0) {
-    return gat_fw<false>("psa_gat_attention_half_fw", drop, dtype, rowptr, col, a_row, a_col, v, bias, bias_heads,
-                         negative_slope, M, N, H, F, nnz, out, stat, workspace, workspace_bytes, stream);
+    return gat_fw<Bf16, false>("psa_gat_attention_half_fw", drop, dtype, rowptr, col, a_row, a_col, v, bias, bias_heads,
+                               negative_slope, M, N, H, F, nnz, out, stat, workspace, workspace_bytes, stream);
   }
-  return gat_fw<true>("psa_gat_attention_half_fw", drop, dtype, rowptr, col, a_row, a_col, v, bias, bias_heads,
-                      negative_slope, M, N, H, F, nnz, out, stat, workspace, workspace_bytes, stream);
+  return gat_fw<Bf16, true>("psa_gat_attention_half_fw", drop, dtype, rowptr, col, a_row, a_col, v, bias, bias_heads,
+                            negative_slope, M, N, H, F, nnz, out, stat, workspace, workspace_bytes, stream);
 }
 
 int psa_gat_attention_half_bw_entries(int dtype, const int64_t* rowptr, const int64_t* col, const void* a_row,
@@ -1112,12 +76,13 @@ int psa_gat_attention_half_bw_entries(int dtype, const int64_t* rowptr, const in
   psa::Drop drop;
   if (!psa::make_drop("psa_gat_attention_half_bw_entries", dropout_p, seed, &drop)) return PSA_ERR_INVALID_ARG;
   if (dropout_p == 0.0) {
-    return gat_bw<false>("psa_gat_attention_half_bw_entries", drop, dtype, rowptr, col, a_row, a_col, v, bias,
-                         bias_heads, negative_slope, grad_out, out, stat, M, N, H, F, nnz, p, dz, workspace,
-                         workspace_bytes, stream);
+    return gat_bw<Bf16, false>("psa_gat_attention_half_bw_entries", drop, dtype, rowptr, col, a_row, a_col, v, bias,
+                               bias_heads, negative_slope, grad_out, out, stat, M, N, H, F, nnz, p, dz, workspace,
+                               workspace_bytes, stream);
   }
-  return gat_bw<true>("psa_gat_attention_half_bw_entries", drop, dtype, rowptr, col, a_row, a_col, v, bias, bias_heads,
-                      negative_slope, grad_out, out, stat, M, N, H, F, nnz, p, dz, workspace, workspace_bytes, stream);
+  return gat_bw<Bf16, true>("psa_gat_attention_half_bw_entries", drop, dtype, rowptr, col, a_row, a_col, v, bias,
+                            bias_heads, negative_slope, grad_out, out, stat, M, N, H, F, nnz, p, dz, workspace,
+                            workspace_bytes, stream);
 }
 
 }  // extern "C"

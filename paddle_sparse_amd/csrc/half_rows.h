@@ -1,6 +1,7 @@
-// Helpers shared by the half-width row kernels (attention_half.hip, spmm_heads_half.hip): a lane's VEC elements
-// of a two-byte operand widened to fp32 on load and rounded once on store, the fp32 partials of the long-row
-// chunks, and the two small host / device utilities both plans use.
+// Helpers shared by the row kernels (attention_kernels.h, spmm_heads_half.hip): a lane's VEC elements of a
+// two-byte operand widened to fp32 on load and rounded once on store, fp32 loads and stores of the same shape (the
+// fp32 operands of attention and the fp32 partials of the long-row chunks), and the two small host / device
+// utilities the plans use.
 #pragma once
 
 #include "half_util.h"
@@ -29,13 +30,17 @@ __device__ __forceinline__ void store_vec(elem_t* p, const float (&src)[VEC]) {
   }
 }
 
-// fp32 partials of the long-row chunks (VEC = 8: two 16-byte accesses)
+// fp32 operands, and the fp32 partials of the long-row chunks whatever the operands are (VEC = 4: one 16-byte
+// access, VEC = 8: two)
 template <int VEC>
 __device__ __forceinline__ void load_f32(const float* p, float (&dst)[VEC]) {
   if constexpr (VEC == 8) {
     const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
     dst[0] = a.x, dst[1] = a.y, dst[2] = a.z, dst[3] = a.w;
     dst[4] = b.x, dst[5] = b.y, dst[6] = b.z, dst[7] = b.w;
+  } else if constexpr (VEC == 4) {
+    const float4 v = *reinterpret_cast<const float4*>(p);
+    dst[0] = v.x, dst[1] = v.y, dst[2] = v.z, dst[3] = v.w;
   } else {
     dst[0] = *p;
   }
@@ -46,6 +51,8 @@ __device__ __forceinline__ void store_f32(float* p, const float (&src)[VEC]) {
   if constexpr (VEC == 8) {
     *reinterpret_cast<float4*>(p) = make_float4(src[0], src[1], src[2], src[3]);
     *reinterpret_cast<float4*>(p + 4) = make_float4(src[4], src[5], src[6], src[7]);
+  } else if constexpr (VEC == 4) {
+    *reinterpret_cast<float4*>(p) = make_float4(src[0], src[1], src[2], src[3]);
   } else {
     *p = src[0];
   }

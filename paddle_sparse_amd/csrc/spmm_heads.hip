@@ -30,9 +30,13 @@
 //
 // Every address is formed in 64-bit arithmetic: no bound on N * H * F * 4.
 #include "common.h"
+#include "half_rows.h"
 #include "long_rows.h"
 
 namespace {
+
+using psa_half::clamp_range;
+using psa_half::pow2_at_least;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
@@ -59,11 +63,6 @@ __device__ __forceinline__ void store_vec(float* p, const float (&src)[VEC]) {
   } else {
     *p = src[0];
   }
-}
-
-__device__ __forceinline__ void clamp_range(int64_t& s, int64_t& e, int64_t nnz) {
-  s = s < 0 ? 0 : s;
-  e = e > nnz ? nnz : e;  // never past the arrays, whatever rowptr holds
 }
 
 // ---- SpMM over per-head values ------------------------------------------------------------------
@@ -423,16 +422,6 @@ int launch_sddmm_heads(const int64_t* rowptr, const int64_t* col, const float* x
   }
   PSA_LAUNCH_CHECK();
   return PSA_OK;
-}
-
-int pow2_at_least(int64_t n, int cap, int* shift) {
-  int p = 1;
-  *shift = 0;
-  while (p < cap && p < n) {
-    p <<= 1;
-    ++*shift;
-  }
-  return p;
 }
 
 // The long-row list at the head of the workspace, its counter zeroed: 0 rows listed so far.
