@@ -885,6 +885,81 @@ int psa_saint_write(const int64_t* rowptr, const int64_t* col, int64_t N, const 
                     const void* workspace, int64_t nnz_out, int64_t* rowptr_out, int64_t* row_out,
                     int64_t* col_out, int64_t* edge_out, psa_stream_t stream);
 
+/* ---- reverse_cuthill_mckee (torch_sparse bandwidth.py) on the pattern of a SQUARE N x N
+ * CSR matrix with sorted rows (rowptr int64[N+1], col int64[nnz]); values are never read.
+ *
+ * deg[i] = rowptr[i+1] - rowptr[i] (stored duplicates and a stored diagonal count).  The
+ * Cuthill-McKee order is built one component at a time: the seed of the next component is
+ * the unvisited node with the smallest (deg, id); from the seed, nodes are taken in order
+ * and each appends its not-yet-visited neighbours sorted by (deg, id), once.  The kernels
+ * build it level by level: the nodes found by one breadth-first level are ordered by
+ * (position of their earliest-placed parent, deg, id), which is the same order.  perm is
+ * that order reversed.  On a non-symmetric pattern the rules run over the stored entries.
+ *
+ * The level loop belongs to the caller (paddle_sparse_amd/ops.py::reverse_cuthill_mckee):
+ *   psa_csr_row_stats            -> n_empty (rows without entries), max_deg   [host read]
+ *   psa_rcm_init(...)            degrees, seeds = stable psa_index_sort of deg = (deg, id)
+ *                                order, the n_empty degree-0 nodes at positions 0..n_empty-1
+ *   repeat
+ *     psa_rcm_small(...)         ONE workgroup runs level after level, starting the next
+ *                                component from seeds whenever a level comes back empty,
+ *                                until all N nodes are placed (status PSA_RCM_DONE) or a
+ *                                level has more than psa_rcm_small_capacity() candidate
+ *                                edges (or more than 2048 frontier nodes): that level is
+ *                                left untouched, status PSA_RCM_HANDOVER    [host read of state]
+ *     while the level [level_lo, level_hi) with `cand` candidate edges is too large:
+ *       psa_rcm_level_count(...) frontier degrees -> psa_count2ptr; tiles of psa_rcm_tile()
+ *                                candidates (a long row spans several workgroups) claim
+ *                                every unseen child for the smallest parent position
+ *                                (atomicMin: order-independent) and count the candidates
+ *                                whose parent won and that are the first of their
+ *                                duplicates -> state[NEW], state[NEXT_CAND] [host read of state]
+ *       psa_rcm_level_write(...) keys parent_local * (max_deg + 1) + deg and the child ids
+ *                                in candidate order ((parent, id) order), a stable
+ *                                psa_sort_pairs_u32, then order / rank; the level becomes
+ *                                [level_hi, level_hi + n_new) with state[NEXT_CAND] candidates
+ *   psa_rcm_finish(...)          perm_out int64[N] = the order reversed
+ * Which path served a level does not change a bit of the result.  No launch waits for
+ * another workgroup (the radix sort's own look-back aside; its fault word is folded into
+ * state[FAULT]); every loop is bounded by N or nnz.
+ *
+ * state: int64[PSA_RCM_STATE_WORDS] on the device, written by psa_rcm_init, =
+ *   { placed, level_lo, level_hi, next_seed, status, cand (candidate edges of the level),
+ *     NEW (nodes the counted level adds), NEXT_CAND (their candidate edges), FAULT (a radix
+ *     pass gave up: the result is invalid), levels served by psa_rcm_small so far, ... }.
+ * workspace: psa_rcm_workspace_bytes(N, nnz) bytes (0 when N is outside [1, 2^31)), 16-byte
+ * aligned, kept from psa_rcm_init to psa_rcm_finish; it includes the scan and sort scratch.
+ * n_empty and max_deg are words 0 and 3 of psa_csr_row_stats.  1 <= N < 2^31. */
+#define PSA_RCM_STATE_WORDS 16
+#define PSA_RCM_DONE 0
+#define PSA_RCM_HANDOVER 1
+#define PSA_RCM_BAD_INPUT 2 /* more nodes found than exist: the rows are not sorted */
+size_t psa_rcm_workspace_bytes(int64_t N, int64_t nnz);
+int psa_rcm_init(const int64_t* rowptr, int64_t N, int64_t nnz, int64_t n_empty, int64_t max_deg, void* workspace,
+                 size_t workspace_bytes, int64_t* state, psa_stream_t stream);
+int psa_rcm_small(const int64_t* rowptr, const int64_t* col, int64_t N, int64_t nnz, int64_t max_deg,
+                  void* workspace, size_t workspace_bytes, int64_t* state, psa_stream_t stream);
+/* level_lo, level_hi, cand: the values of the last host read of state (1 <= cand <= nnz). */
+int psa_rcm_level_count(const int64_t* rowptr, const int64_t* col, int64_t N, int64_t nnz, int64_t level_lo,
+                        int64_t level_hi, int64_t cand, void* workspace, size_t workspace_bytes, int64_t* state,
+                        psa_stream_t stream);
+/* n_new: state[NEW] as read after psa_rcm_level_count of the same level (0 allowed: the
+ * level found nothing, the component is complete and psa_rcm_small starts the next). */
+int psa_rcm_level_write(const int64_t* rowptr, const int64_t* col, int64_t N, int64_t nnz, int64_t level_lo,
+                        int64_t level_hi, int64_t cand, int64_t n_new, int64_t max_deg, void* workspace,
+                        size_t workspace_bytes, int64_t* state, psa_stream_t stream);
+int psa_rcm_finish(int64_t N, int64_t nnz, const void* workspace, size_t workspace_bytes, int64_t* perm_out,
+                   psa_stream_t stream);
+/* Candidate edges of a level that psa_rcm_small takes under the current variant (4096 by
+ * default), and the candidates per workgroup of the large path (1024). */
+int64_t psa_rcm_small_capacity(void);
+int64_t psa_rcm_tile(void);
+/* Test/bench hook: 0 = default, 1 = every level through the large path (capacity 0: the
+ * small launch only starts components), 2 = the small path with a capacity of 8 candidate
+ * edges, so that both paths and the hand-over in each direction happen at tiny sizes.
+ * Returns the previous value.  All produce the same bits. */
+int psa_rcm_set_variant(int variant);
+
 /* ---- segmented softmax of stored values (the attention path: softmax over the entries of
  * every row or column of a sparse matrix), fp32.  src, out: [n, D] row-major (D = 1 for
  * scalar values), any 4-byte alignment; indptr int64[nseg + 1] with indptr[nseg] <= n.

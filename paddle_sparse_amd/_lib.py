@@ -154,6 +154,17 @@ SIGNATURES = {
                                 c_void_p]),
     "psa_saint_write": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                 c_void_p, c_void_p, c_void_p, c_void_p]),
+    "psa_rcm_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "psa_rcm_init": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "psa_rcm_small": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "psa_rcm_level_count": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
+                                    c_size_t, c_void_p, c_void_p]),
+    "psa_rcm_level_write": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                    c_void_p, c_size_t, c_void_p, c_void_p]),
+    "psa_rcm_finish": (c_int, [c_int64, c_int64, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "psa_rcm_small_capacity": (c_int64, []),
+    "psa_rcm_tile": (c_int64, []),
+    "psa_rcm_set_variant": (c_int, [c_int]),
     "psa_segment_softmax_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "psa_segment_softmax": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                     c_size_t, c_void_p]),

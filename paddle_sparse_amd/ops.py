@@ -1573,6 +1573,87 @@ def saint_subgraph(rowptr: torch.Tensor, col: torch.Tensor, node_idx: torch.Tens
     return rowptr_out, out[0], out[1], out[2], flags
 
 
+# ---- reverse_cuthill_mckee (csrc/rcm.hip) ---------------------------------------------------------
+
+RCM_DONE, RCM_HANDOVER, RCM_BAD_INPUT = 0, 1, 2
+
+
+def rcm_set_variant(variant: int) -> int:
+    """Test/bench hook: 0 = default, 1 = every level through the large path, 2 = the small path
+    with a capacity of 8 candidate edges; returns the previous one.  All give the same bits."""
+    return _lib.load().psa_rcm_set_variant(int(variant))
+
+
+def rcm_small_capacity() -> int:
+    """Candidate edges of a level that the one-workgroup path takes under the current variant."""
+    return int(_lib.load().psa_rcm_small_capacity())
+
+
+def rcm_tile() -> int:
+    """Candidates per workgroup of the large path."""
+    return int(_lib.load().psa_rcm_tile())
+
+
+def reverse_cuthill_mckee(rowptr: torch.Tensor, col: torch.Tensor, stats: Optional[dict] = None) -> torch.Tensor:
+    """perm int64[N]: the reverse Cuthill-McKee ordering of the square sorted CSR pattern
+    (rowptr int64[N+1], col int64[nnz]) — scipy's algorithm with its ties fixed: seeds and
+    neighbours in (degree, id) order, degree = stored entries of the row.  Built
+    on the device: levels of up to rcm_small_capacity() candidate edges run inside one
+    workgroup, level after level, with one host read per launch; a larger level is a fixed
+    launch sequence with one host read.  Which path served a level does not change the
+    result.  stats (a dict, optional) receives the level and host-read counts.
+    Not capturable in a graph: the launch sequence depends on the data.  N < 2^31."""
+    rowptr, col = _index(rowptr, "rowptr"), _index(col, "col")
+    if rowptr.numel() < 1:
+        raise ValueError("rowptr must have at least one element")
+    N, nnz, dev = rowptr.numel() - 1, col.numel(), rowptr.device
+    if N >= 2**31:
+        raise ValueError(f"reverse_cuthill_mckee needs N < 2^31 (got {N})")
+    count = {"host_reads": 0, "small_launches": 0, "small_levels": 0, "large_levels": 0}
+    if stats is not None:
+        stats.update(count)
+    if N == 0 or nnz == 0:  # every node is its own component, in id order
+        return torch.arange(N - 1, -1, -1, dtype=torch.int64, device=dev)
+    lib = _lib.load()
+    n_empty, _, _, max_deg = csr_row_stats(rowptr)
+    count["host_reads"] += 1
+    ws = _workspace(lib.psa_rcm_workspace_bytes(N, nnz), dev)
+    state = torch.empty(16, dtype=torch.int64, device=dev)
+    perm = torch.empty(N, dtype=torch.int64, device=dev)
+    cap = lib.psa_rcm_small_capacity()
+    a = (_ptr(rowptr), _ptr(col), N, nnz)
+    w = (_ptr(ws), ws.numel(), _ptr(state))
+    with _on(dev):
+        check(lib.psa_rcm_init(_ptr(rowptr), N, nnz, n_empty, max_deg, *w, _stream()))
+        for _ in range(N + 1):  # every small launch ends the order or hands over a level that places a node
+            check(lib.psa_rcm_small(*a, max_deg, *w, _stream()))
+            placed, lo, hi, _, status, cand, _, _, fault, small_levels = state.tolist()[:10]
+            count["host_reads"] += 1
+            count["small_launches"] += 1
+            count["small_levels"] = small_levels
+            if fault or status != RCM_HANDOVER:
+                break
+            while True:
+                check(lib.psa_rcm_level_count(*a, lo, hi, cand, *w, _stream()))
+                n_new, next_cand = state[6:8].tolist()
+                count["host_reads"] += 1
+                count["large_levels"] += 1
+                check(lib.psa_rcm_level_write(*a, lo, hi, cand, n_new, max_deg, *w, _stream()))
+                lo, hi, cand = hi, hi + n_new, next_cand
+                if n_new == 0 or cand <= cap:
+                    break
+        if stats is not None:
+            stats.update(count)
+        if fault:
+            raise HipCoreError("reverse_cuthill_mckee: an inter-workgroup wait of a radix pass gave up; "
+                               "the order is invalid")
+        if status != RCM_DONE or placed != N:
+            raise ValueError("reverse_cuthill_mckee: the level search placed "
+                             f"{placed} of {N} nodes (status {status}); are the rows of the matrix sorted?")
+        check(lib.psa_rcm_finish(N, nnz, _ptr(ws), ws.numel(), _ptr(perm), _stream()))
+    return perm
+
+
 # ---- the attention path: segmented softmax (csrc/softmax.hip) and sddmm ----------------------------
 
 def _softmax_operands(a: torch.Tensor, name: str, indptr: torch.Tensor, perm: Optional[torch.Tensor]):
