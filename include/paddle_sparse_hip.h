@@ -960,6 +960,80 @@ int64_t psa_rcm_tile(void);
  * Returns the previous value.  All produce the same bits. */
 int psa_rcm_set_variant(int variant);
 
+/* ---- neighbor_sample (torch_sparse neighbor_sample, CPU only upstream): multi-hop,
+ * layer-wise neighbour sampling of a SQUARE N x N CSR matrix with sorted rows, with one
+ * relabel map for the whole call.
+ *
+ * n_id starts as the seeds (distinct, inside [0, N)); local id = position in n_id.  Hop l
+ * expands the frontier, the nodes appended during hop l - 1 (hop 1: the seeds), local ids
+ * [begin, end); every node is expanded at most once per call.  A frontier node at local id
+ * i with deg stored entries makes the picks of psa_sample_count / psa_sample_select for
+ * (deg, num_neighbors, replace).  Random-stream contract: draw t of the node at LOCAL ID i
+ * is randint(seed, i, t, .) of psa_sample_select (stream i, draw t; Floyd's walk draws
+ * randint(seed, i, t, deg - k + t)), whatever the hop: local ids are unique across hops, so
+ * one seed serves all of them, and hop 1 makes the picks of sample_adj(seeds, k, replace,
+ * seed).  Slot order within a hop is (frontier position, t).  A picked column without a
+ * local id gets the next one in order of its first slot and is appended to n_id; one that
+ * has a local id (a seed, a node of an earlier or of the same hop) keeps it.  Every slot
+ * emits (row' = i, col' = local id of the column, e = position in the matrix's storage).
+ *
+ * The hop loop belongs to the caller (paddle_sparse_amd/ops.py::neighbor_sample):
+ *   psa_neighbor_init(...)        fill the map when `fresh`; place and check the seeds
+ *   per hop with num_neighbors != 0 and a non-empty frontier:
+ *     num_neighbors < 0 only: psa_neighbor_hop_count -> psa_count2ptr -> frontier_ptr,
+ *                                 slots = frontier_ptr[F]                  [host read]
+ *     num_neighbors >= 0:         slots = F * num_neighbors, the bound the grid covers
+ *     psa_neighbor_hop_pick(...)  picks, one atomicMax claim per slot (the smallest slot
+ *                                 wins whatever the arrival order), one scan;
+ *                                 state = {E_l, new_l, flags}              [host read]
+ *     psa_neighbor_hop_write(...) n_id_new int64[new_l] (the next frontier, local ids
+ *                                 [end, end + new_l)), row_out / col_out / edge_out
+ *                                 int64[E_l] in slot order, the map finalised
+ *   psa_neighbor_reset(...)       map[n_id[j]] = unseen: the workspace is clean again
+ *   the caller sorts (stable) by row' * n + col' with psa_index_sort and builds rowptr'
+ *   with psa_ind2ptr.
+ * state: int64[PSA_NEIGHBOR_STATE_WORDS] on the device, zeroed by psa_neighbor_init;
+ * state[2] collects PSA_NEIGHBOR_DUP_SEED, PSA_NEIGHBOR_SEED_OUTSIDE (such a seed is
+ * skipped and has no entries) and PSA_NEIGHBOR_COL_OUTSIDE (a stored column outside
+ * [0, N): its slot is dropped); with a flag up the call must end with psa_neighbor_reset
+ * over the seeds, the nodes appended so far AND the slots of the hop just picked (its
+ * claims are in the map).
+ * workspace: psa_neighbor_workspace_bytes(N) bytes, 16-byte aligned: the map int32[N].  It
+ * may be kept between calls: after psa_neighbor_reset it is clean and the next
+ * psa_neighbor_init takes fresh = 0, so nothing sized N runs per call.
+ * hop_workspace: psa_neighbor_hop_workspace_bytes(slots) bytes, 16-byte aligned, kept
+ * from psa_neighbor_hop_pick to psa_neighbor_hop_write (or the reset of an abandoned hop).
+ * N, the node count and slots stay below 2^31 (the size functions return 0 otherwise).
+ * Deterministic; no launch waits for another workgroup; not capturable in a graph. */
+#define PSA_NEIGHBOR_STATE_WORDS 8
+#define PSA_NEIGHBOR_DUP_SEED 1
+#define PSA_NEIGHBOR_SEED_OUTSIDE 2
+#define PSA_NEIGHBOR_COL_OUTSIDE 4
+size_t psa_neighbor_workspace_bytes(int64_t N);
+size_t psa_neighbor_hop_workspace_bytes(int64_t slots);
+int psa_neighbor_init(const int64_t* seeds, int64_t S, int64_t N, int fresh, void* workspace, size_t workspace_bytes,
+                      int64_t* state, psa_stream_t stream);
+/* counts[f] = stored entries of frontier node f (0 for a node outside the matrix). */
+int psa_neighbor_hop_count(const int64_t* rowptr, int64_t N, const int64_t* frontier, int64_t F, int64_t* counts,
+                           psa_stream_t stream);
+/* frontier: int64[F], the nodes at local ids [begin, begin + F); frontier_ptr: int64[F+1],
+ * read when num_neighbors < 0 only (NULL otherwise); num_neighbors != 0, F >= 1, slots >= 1. */
+int psa_neighbor_hop_pick(const int64_t* rowptr, const int64_t* col, int64_t N, const int64_t* frontier, int64_t F,
+                          const int64_t* frontier_ptr, int64_t begin, int64_t num_neighbors, int replace,
+                          uint64_t seed, int64_t slots, void* workspace, void* hop_workspace,
+                          size_t hop_workspace_bytes, int64_t* state, psa_stream_t stream);
+/* n_edges, n_new: state[0], state[1] as read after psa_neighbor_hop_pick of the same hop.
+ * row_out, col_out and edge_out may be NULL together: only n_id_new and the map are then
+ * written (a caller that wants the node set alone). */
+int psa_neighbor_hop_write(const int64_t* col, int64_t begin, int64_t end, int64_t num_neighbors, int64_t slots,
+                           int64_t n_edges, int64_t n_new, void* workspace, const void* hop_workspace,
+                           int64_t* n_id_new, int64_t* row_out, int64_t* col_out, int64_t* edge_out,
+                           psa_stream_t stream);
+/* ids: int64[n] nodes whose map entries are cleared (entries outside [0, N) are skipped);
+ * slots > 0: also the columns claimed by the slots of the hop held in hop_workspace. */
+int psa_neighbor_reset(const int64_t* ids, int64_t n, int64_t N, const int64_t* col, const void* hop_workspace,
+                       int64_t slots, void* workspace, psa_stream_t stream);
+
 /* ---- segmented softmax of stored values (the attention path: softmax over the entries of
  * every row or column of a sparse matrix), fp32.  src, out: [n, D] row-major (D = 1 for
  * scalar values), any 4-byte alignment; indptr int64[nseg + 1] with indptr[nseg] <= n.

@@ -63,6 +63,7 @@ if not _running_the_builder():
         ("diag", ("remove_diag", "set_diag", "fill_diag", "get_diag")),
         ("rw", ("random_walk",)),
         ("saint", ("saint_subgraph",)),
+        ("neighbor", ("neighbor_sample", "NeighborSampler")),
         ("bandwidth", ("reverse_cuthill_mckee",)),
         ("softmax", ("softmax",)),
         ("sddmm", ("sddmm",)),

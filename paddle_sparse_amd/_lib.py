@@ -165,6 +165,15 @@ SIGNATURES = {
     "psa_rcm_small_capacity": (c_int64, []),
     "psa_rcm_tile": (c_int64, []),
     "psa_rcm_set_variant": (c_int, [c_int]),
+    "psa_neighbor_workspace_bytes": (c_size_t, [c_int64]),
+    "psa_neighbor_hop_workspace_bytes": (c_size_t, [c_int64]),
+    "psa_neighbor_init": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "psa_neighbor_hop_count": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    "psa_neighbor_hop_pick": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int,
+                                      c_uint64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "psa_neighbor_hop_write": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "psa_neighbor_reset": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "psa_segment_softmax_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "psa_segment_softmax": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                     c_size_t, c_void_p]),

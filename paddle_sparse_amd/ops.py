@@ -1573,6 +1573,153 @@ def saint_subgraph(rowptr: torch.Tensor, col: torch.Tensor, node_idx: torch.Tens
     return rowptr_out, out[0], out[1], out[2], flags
 
 
+# ---- neighbor_sample (csrc/neighbor.hip) ------------------------------------------------------------
+
+NEIGHBOR_DUP_SEED, NEIGHBOR_SEED_OUTSIDE, NEIGHBOR_COL_OUTSIDE = 1, 2, 4
+
+
+class NeighborWorkspace:
+    """The relabel map of neighbor_sample (int32[N] on the device) and whether it is clean.
+    A clean map is reused as it is: a call then costs stores per touched node, not per node."""
+
+    def __init__(self, num_nodes: int, device):
+        nbytes = _lib.load().psa_neighbor_workspace_bytes(int(num_nodes))
+        if nbytes == 0:
+            raise ValueError(f"neighbor_sample needs N < 2^31 (got {num_nodes})")
+        self.num_nodes, self.buf, self.clean = int(num_nodes), _workspace(nbytes, device), False
+
+
+def neighbor_sample(rowptr: torch.Tensor, col: torch.Tensor, seeds: torch.Tensor, num_neighbors, replace: bool = False,
+                    seed: int = 0, workspace: Optional[NeighborWorkspace] = None, stats: Optional[dict] = None,
+                    want_edges: bool = True):
+    """Multi-hop neighbour sampling of a square sorted CSR matrix: returns
+    (n_id int64[n], rowptr' int64[n+1], col' int64[E], e_id int64[E], nodes_per_hop,
+    edges_per_hop), the entries sorted (stable) by (row', col').  seeds int64[S], distinct
+    (ValueError) and inside the matrix (IndexError); num_neighbors: one fan-out >= -1 per
+    hop; -1 takes every entry.  A hop with fan-out k >= 0 is sized by its bound, (frontier
+    nodes) * k slots of 28 bytes, before anything is counted, and that bound stays below
+    2^31: to take all entries pass -1, which counts first, not a large k.
+    Draw t of the node at local id i comes from stream i of `seed`, whatever the hop.
+    One host read per hop (two when the fan-out is -1) and one behind the sort; stats (a
+    dict, optional) receives host_reads and hops_run.  workspace: a NeighborWorkspace kept
+    between calls.  want_edges=False stops after the node set (the caller induces the
+    subgraph): no hop writes its entries and the edge outputs are None.  Not capturable in a graph: the sizes depend on
+    the data.  N, n < 2^31."""
+    rowptr, col, seeds = _index(rowptr, "rowptr"), _index(col, "col"), _index(seeds, "seeds")
+    if rowptr.numel() < 1:
+        raise ValueError("rowptr must have at least one element")
+    fanouts = [int(k) for k in num_neighbors]
+    if any(k < -1 for k in fanouts):
+        raise ValueError(f"num_neighbors must be >= -1 (got {fanouts})")
+    N, S, dev = rowptr.numel() - 1, seeds.numel(), rowptr.device
+    if N >= 2**31 or S >= 2**31:
+        raise ValueError(f"neighbor_sample needs N < 2^31 and fewer than 2^31 seeds (got {N}, {S})")
+    ws = workspace if workspace is not None else NeighborWorkspace(N, dev)
+    if ws.num_nodes != N or ws.buf.device != dev:
+        raise ValueError("the workspace belongs to another matrix or device")
+    lib = _lib.load()
+    rep, seed = int(bool(replace)), int(seed) & (2**64 - 1)
+    count = {"host_reads": 0, "hops_run": 0}
+    state = torch.empty(8, dtype=torch.int64, device=dev)
+    empty = torch.empty(0, dtype=torch.int64, device=dev)
+    nodes, rows, cols, edges = [seeds], [], [], []
+    nodes_per_hop, edges_per_hop = [S], []
+
+    def reset(hop_ws=None, slots=0):
+        ids = torch.cat(nodes) if len(nodes) > 1 else nodes[0]
+        check(lib.psa_neighbor_reset(_ptr(ids), ids.numel(), N, _ptr(col), _ptr(hop_ws), slots, _ptr(ws.buf),
+                                     _stream()))
+        ws.clean = True
+        return ids
+
+    def raise_on(flags, hop_ws=None, slots=0):
+        if not flags:
+            return
+        reset(hop_ws, slots)
+        if stats is not None:
+            stats.update(count)
+        if flags & NEIGHBOR_SEED_OUTSIDE:
+            raise IndexError(f"neighbor_sample: a seed lies outside [0, {N})")
+        if flags & NEIGHBOR_DUP_SEED:
+            raise ValueError("neighbor_sample: the seeds must be distinct")
+        raise ValueError(f"neighbor_sample: a stored column lies outside [0, {N})")
+
+    with _on(dev):
+        fresh, ws.clean = not ws.clean, False  # stays False if anything below raises: the next call refills
+        check(lib.psa_neighbor_init(_ptr(seeds), S, N, int(fresh), _ptr(ws.buf), ws.buf.numel(), _ptr(state), _stream()))
+        begin, end, frontier, checked = 0, S, seeds, False
+        for k in fanouts:
+            F, slots, fptr = (end - begin if col.numel() else 0), 0, None  # a matrix without entries: nothing to pick
+            if F > 0 and k < 0:
+                counts = torch.empty(F, dtype=torch.int64, device=dev)
+                check(lib.psa_neighbor_hop_count(_ptr(rowptr), N, _ptr(frontier), F, _ptr(counts), _stream()))
+                fptr = count2ptr(counts)
+                slots = int(fptr[-1].item())
+                count["host_reads"] += 1
+            elif F > 0:
+                slots = F * k
+            n_edges = n_new = 0
+            new = empty
+            if slots > 0:
+                nbytes = lib.psa_neighbor_hop_workspace_bytes(slots)
+                if nbytes == 0:
+                    reset()
+                    raise ValueError(f"neighbor_sample: a hop of {slots} picks does not fit 2^31")
+                hop_ws = _workspace(nbytes, dev)
+                check(lib.psa_neighbor_hop_pick(_ptr(rowptr), _ptr(col), N, _ptr(frontier), F, _ptr(fptr), begin, k, rep,
+                                                seed, slots, _ptr(ws.buf), _ptr(hop_ws), hop_ws.numel(), _ptr(state),
+                                                _stream()))
+                n_edges, n_new, flags = state[:3].tolist()  # the hop's host read
+                count["host_reads"] += 1
+                count["hops_run"] += 1
+                checked = True
+                raise_on(flags, hop_ws, slots)
+                if end + n_new >= 2**31:
+                    reset(hop_ws, slots)
+                    raise ValueError("neighbor_sample: the sample has 2^31 nodes or more")
+                new = torch.empty(n_new, dtype=torch.int64, device=dev)
+                out = torch.empty((3, n_edges), dtype=torch.int64, device=dev) if want_edges else (None,) * 3
+                check(lib.psa_neighbor_hop_write(_ptr(col), begin, end, k, slots, n_edges, n_new, _ptr(ws.buf),
+                                                 _ptr(hop_ws), _ptr(new), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                                 _stream()))
+                if n_edges > 0 and want_edges:
+                    rows.append(out[0]), cols.append(out[1]), edges.append(out[2])
+                if n_new > 0:
+                    nodes.append(new)
+            nodes_per_hop.append(n_new)
+            edges_per_hop.append(n_edges)
+            begin, end, frontier = end, end + n_new, new
+        if not checked and S > 0:
+            flags = int(state[2].item())
+            count["host_reads"] += 1
+            raise_on(flags)
+        n_id = reset()
+        n, E = end, sum(edges_per_hop)
+        if not want_edges:
+            if stats is not None:
+                stats.update(count)
+            return n_id, None, None, None, nodes_per_hop, None
+        if E == 0:
+            if stats is not None:
+                stats.update(count)
+            return n_id, torch.zeros(n + 1, dtype=torch.int64, device=dev), empty, empty.clone(), nodes_per_hop, edges_per_hop
+        row = torch.cat(rows) if len(rows) > 1 else rows[0]
+        col_new = torch.cat(cols) if len(cols) > 1 else cols[0]
+        e_raw = torch.cat(edges) if len(edges) > 1 else edges[0]
+        keys, _ = make_keys(row, col_new, n)
+        keys, perm = index_sort(keys, n * n, with_sorted_inputs=True, check=True)  # stable: ties keep slot order
+        count["host_reads"] += 1
+        if stats is not None:
+            stats.update(count)
+        row, col_new = split_keys(keys, n)
+        # the nodes of the last hop that appended any were never expanded: rows from `begin` on are empty.  They are
+        # filled here; as the tail of psa_ind2ptr they would be one run, which a single wave writes
+        rowptr_out = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        check(lib.psa_ind2ptr(_ptr(row), E, begin, _ptr(rowptr_out), _stream()))
+        rowptr_out[begin + 1:] = E
+        return n_id, rowptr_out, col_new, _gather_rows_raw(e_raw, perm), nodes_per_hop, edges_per_hop
+
+
 # ---- reverse_cuthill_mckee (csrc/rcm.hip) ---------------------------------------------------------
 
 RCM_DONE, RCM_HANDOVER, RCM_BAD_INPUT = 0, 1, 2
