@@ -24,7 +24,10 @@ attn_dropout_mask_kernel(int64_t total, int64_t H, uint64_t seed, uint32_t T, un
 
 extern "C" {
 
-size_t psa_attention_workspace_bytes(int64_t nnz, int64_t H, int64_t F) { return fw_workspace_bytes(nnz, H, F); }
+size_t psa_attention_workspace_bytes(int64_t nnz, int64_t H, int64_t F) {
+  if (nnz <= psa::kLongRow || H <= 0 || F <= 0) return 0;  // no row can be long
+  return long_layout(nullptr, nnz, H, F, true).bytes;
+}
 
 int psa_attention_fw(const int64_t* rowptr, const int64_t* col, const float* q, const float* k, const float* v,
                      const float* bias, int64_t bias_heads, float scale, int64_t M, int64_t N, int64_t H, int64_t K,

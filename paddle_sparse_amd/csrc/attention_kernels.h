@@ -768,16 +768,6 @@ DotGeo dot_geo(int64_t H, int Hb, int64_t K, int vec) {
   return g;
 }
 
-// The partials are fp32 whatever the operands are: one workspace formula (psa_attention_workspace_bytes).
-size_t part_bytes(int64_t nnz, int64_t D) {
-  return psa::align256(sizeof(float) * static_cast<size_t>(psa::max_long_chunks(nnz)) * static_cast<size_t>(D));
-}
-
-size_t fw_workspace_bytes(int64_t nnz, int64_t H, int64_t F) {
-  if (nnz <= psa::kLongRow || H <= 0 || F <= 0) return 0;  // no row can be long
-  return psa::long_list_bytes(nnz) + part_bytes(nnz, H * F) + part_bytes(nnz, H * 2);
-}
-
 int chunk_blocks(int64_t n) {
   const int64_t b = psa::ceil_div(n, kWaves);
   return static_cast<int>(b > kMaxChunkBlocks ? kMaxChunkBlocks : b);
@@ -793,32 +783,34 @@ int chunk_blocks(int64_t n) {
   } while (0)
 
 // What a call has of the workspace: all NULL when no row can be long.
-struct LongRows {
-  unsigned long long* ctr = nullptr;
-  psa::LongEntry* list = nullptr;
+struct LongRows : psa::LongList {
   float* part = nullptr;   // forward only: [chunks, H * F]
   float* pstat = nullptr;  // forward only: [chunks, H, 2]
+  size_t bytes = 0;
 };
 
-// The long-row list at the head of the workspace, its counter zeroed (0 rows listed so far), and for the forward
-// (partials) the two arrays of the chunks behind it.
+// {list} and, for the forward (partials), the two arrays of the chunks behind it.  The partials are fp32 whatever
+// the operands are: one layout, whose full form is psa_attention_workspace_bytes.
+LongRows long_layout(void* workspace, int64_t nnz, int64_t H, int64_t F, bool partials) {
+  psa::Carver c(workspace);
+  LongRows lr;
+  psa::take_long_list(c, nnz, &lr);
+  if (partials) {
+    lr.part = psa::take_long_chunks<float>(c, nnz, H * F);
+    lr.pstat = psa::take_long_chunks<float>(c, nnz, H * 2);
+  }
+  lr.bytes = c.off;
+  return lr;
+}
+
+// The layout over the caller's workspace, checked, its counter zeroed (0 rows listed so far).
 int take_long_rows(const char* who, void* workspace, size_t have, int64_t nnz, int64_t H, int64_t F, bool partials,
                    hipStream_t s, LongRows* lr) {
   if (nnz <= psa::kLongRow) return PSA_OK;
-  if (workspace == nullptr || have < (partials ? fw_workspace_bytes(nnz, H, F) : psa::long_list_bytes(nnz))) {
-    psa::set_error(std::string(who) + ": workspace too small");
-    return PSA_ERR_WORKSPACE;
-  }
-  ATTN_REQUIRE(psa::aligned(workspace, 16), "workspace must be 16-byte aligned");
-  lr->ctr = static_cast<unsigned long long*>(workspace);
-  lr->list = reinterpret_cast<psa::LongEntry*>(static_cast<char*>(workspace) + 256);
-  PSA_ZERO(lr->ctr, 8, s);
-  if (partials) {
-    char* w = static_cast<char*>(workspace) + psa::long_list_bytes(nnz);
-    lr->part = reinterpret_cast<float*>(w);
-    lr->pstat = reinterpret_cast<float*>(w + part_bytes(nnz, H * F));
-  }
-  return PSA_OK;
+  const LongRows w = long_layout(workspace, nnz, H, F, partials);
+  const int rc = psa::begin_long_rows(who, workspace, have, w.bytes, w.ctr, s);
+  if (rc == PSA_OK) *lr = w;
+  return rc;
 }
 
 // The checks every entry point begins with; the GAT forms pass K = 1 and their messages do not name it.

@@ -44,8 +44,6 @@ constexpr int kSmallWaves = kSmallThreads / 64;
 enum { R_SUM = 0, R_MEAN = 1, R_MIN = 2, R_MAX = 3 };
 enum { F_RANGE = 1, F_UNSORTED = 2, F_SORT_FAULT = 4 };  // status[1] bits
 
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 int bits_for(int64_t max_value) {  // bits needed for keys in [0, max_value)
   int b = 0;
   uint64_t v = max_value > 1 ? static_cast<uint64_t>(max_value - 1) : 0;
@@ -420,27 +418,21 @@ struct ChainWs {
 
 ChainWs carve(void* base, int64_t n, int64_t M, int64_t N) {
   ChainWs w{};
-  char* p = static_cast<char*>(base);
-  size_t off = 256;
+  psa::Carver c(base);
   const size_t nn = static_cast<size_t>(n > 0 ? n : 1);
-  auto take = [&](size_t bytes) {
-    char* q = p ? p + off : nullptr;
-    off += align_up(bytes, 256);
-    return q;
-  };
-  w.status = reinterpret_cast<int64_t*>(p);
-  w.a = reinterpret_cast<int64_t*>(take(8 * nn));
-  w.b = reinterpret_cast<int64_t*>(take(8 * nn));
-  w.ptr = reinterpret_cast<int64_t*>(take(8 * (nn + 1)));
-  w.perm = reinterpret_cast<int64_t*>(take(8 * nn));
+  w.status = c.take<int64_t>(4, 256);
+  w.a = c.take<int64_t>(nn, 256);
+  w.b = c.take<int64_t>(nn, 256);
+  w.ptr = c.take<int64_t>(nn + 1, 256);
+  w.perm = c.take<int64_t>(nn, 256);
   if (!small_path(n, M, N)) {
     const int64_t max_value = (M > 0 && N > 0 && static_cast<double>(M) * static_cast<double>(N) < 9.0e18) ? M * N : INT64_MAX;
     w.sort_bytes = psa_index_sort_workspace_bytes(n, max_value);
-    w.sort_ws = take(w.sort_bytes);
+    w.sort_ws = c.take<char>(w.sort_bytes, 256);
     w.uniq_bytes = psa_unique_workspace_bytes(n);
-    w.uniq_ws = take(w.uniq_bytes);
+    w.uniq_ws = c.take<char>(w.uniq_bytes, 256);
   }
-  w.total = off;
+  w.total = c.off;
   return w;
 }
 

@@ -26,6 +26,25 @@ inline bool aligned(const void* p, size_t a) {
   return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0;
 }
 
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// Walks the regions of a caller-allocated workspace in order.  Every workspace has ONE layout
+// function that takes its regions from a Carver: over a real base it hands out the pointers,
+// over a NULL base it only adds up `off`, which is the public *_workspace_bytes.  Size and
+// layout cannot disagree that way.
+struct Carver {
+  char* base;
+  size_t off = 0;
+  explicit Carver(void* workspace) : base(static_cast<char*>(workspace)) {}
+  // `count` elements of T, the region padded to a multiple of `align` bytes
+  template <typename T>
+  T* take(size_t count, size_t align) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += align_up(sizeof(T) * count, align);
+    return p;
+  }
+};
+
 // Zero-fill by a kernel of the core (4-byte aligned pointer and size).  Used
 // instead of hipMemsetAsync everywhere: memset NODES of a captured HIP graph
 // replay wrongly from the second launch on with the ROCm runtime torch 2.10

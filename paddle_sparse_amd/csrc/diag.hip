@@ -298,14 +298,29 @@ int64_t clamp_k(int64_t k, int64_t M, int64_t N) {
   return k;
 }
 
-size_t align16(size_t b) { return (b + 15) & ~size_t{15}; }
+// {position of every row's diagonal entry [M] (psa_diag_write reads it), scratch of the row-count scan}
+struct DiagWs {
+  int64_t* dpos;
+  char* scan;
+  size_t scan_bytes, bytes;
+};
+
+DiagWs diag_layout(void* workspace, int64_t M) {
+  psa::Carver c(workspace);
+  DiagWs w;
+  w.dpos = c.take<int64_t>(static_cast<size_t>(M > 0 ? M : 1), 16);
+  w.scan_bytes = psa_count2ptr_workspace_bytes(M);
+  w.scan = c.take<char>(w.scan_bytes, 1);
+  w.bytes = c.off;
+  return w;
+}
 
 }  // namespace
 
 extern "C" {
 
 size_t psa_diag_workspace_bytes(int64_t M) {
-  return align16(sizeof(int64_t) * static_cast<size_t>(M > 0 ? M : 1)) + psa_count2ptr_workspace_bytes(M);
+  return diag_layout(nullptr, M).bytes;
 }
 
 int psa_diag_count(const int64_t* rowptr, const int64_t* col, int64_t M, int64_t N, int64_t k, int insert,
@@ -315,7 +330,8 @@ int psa_diag_count(const int64_t* rowptr, const int64_t* col, int64_t M, int64_t
   PSA_REQUIRE(rowptr != nullptr && rowptr_out != nullptr, "NULL pointer");
   PSA_REQUIRE(M == 0 || rowcount_out != nullptr, "rowcount_out is NULL");
   PSA_REQUIRE(colcount == nullptr || N == 0 || colcount_out != nullptr, "colcount_out is NULL");
-  if (workspace == nullptr || workspace_bytes < psa_diag_workspace_bytes(M)) {
+  const DiagWs w = diag_layout(workspace, M);
+  if (workspace == nullptr || workspace_bytes < w.bytes) {
     psa::set_error("psa_diag_count: workspace too small");
     return PSA_ERR_WORKSPACE;
   }
@@ -327,11 +343,10 @@ int psa_diag_count(const int64_t* rowptr, const int64_t* col, int64_t M, int64_t
     PSA_REQUIRE(blocks <= 0x7fffffff, "M too large for one launch");
     hipLaunchKernelGGL(diag_count_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, s, rowptr, col,
                        M, N, k, insert ? 1 : 0, colcount, rowcount_out, colcount_out,
-                       static_cast<int64_t*>(workspace));
+                       w.dpos);
     PSA_LAUNCH_CHECK();
   }
-  char* scan_ws = static_cast<char*>(workspace) + align16(sizeof(int64_t) * static_cast<size_t>(M > 0 ? M : 1));
-  return psa_count2ptr(rowcount_out, M, rowptr_out, scan_ws, psa_count2ptr_workspace_bytes(M), stream);
+  return psa_count2ptr(rowcount_out, M, rowptr_out, w.scan, w.scan_bytes, stream);
 }
 
 int psa_diag_write(const int64_t* rowptr, const int64_t* col, const void* value, int64_t row_bytes,

@@ -32,10 +32,64 @@ struct LongEntry {
 
 inline int64_t max_long_rows(int64_t nnz) { return nnz / (kLongRow + 1) + 1; }
 inline int64_t max_long_chunks(int64_t nnz) { return nnz / kLongChunk + max_long_rows(nnz) + 1; }
-inline size_t align256(size_t x) { return (x + 255) / 256 * 256; }
-// bytes of {counter (256-B slot), list}
+
+// Head of every long-row workspace: {counter in a 256-byte slot, list}.  A family's layout
+// function takes this first and its own partials behind it from the same Carver.
+struct LongList {
+  unsigned long long* ctr = nullptr;  // {rows << 32 | chunks}, zeroed every call
+  LongEntry* list = nullptr;
+};
+
+inline void take_long_list(Carver& c, int64_t nnz, LongList* l) {
+  l->ctr = c.take<unsigned long long>(1, 256);
+  l->list = c.take<LongEntry>(static_cast<size_t>(max_long_rows(nnz)), 256);
+}
+
+// one region of `per_chunk` elements of T for every chunk there can be
+template <typename T>
+inline T* take_long_chunks(Carver& c, int64_t nnz, int64_t per_chunk) {
+  return c.take<T>(static_cast<size_t>(max_long_chunks(nnz)) * static_cast<size_t>(per_chunk), 256);
+}
+
+// the workspace that is nothing but the list
 inline size_t long_list_bytes(int64_t nnz) {
-  return 256 + align256(sizeof(LongEntry) * static_cast<size_t>(max_long_rows(nnz)));
+  Carver c(nullptr);
+  LongList l;
+  take_long_list(c, nnz, &l);
+  return c.off;
+}
+
+// {list, fp32 partials [chunks, D]}: the layout of the passes whose chunk waves leave one fp32
+// row each (spmm_heads.hip, spmm_heads_half.hip, spmm_half_bw.hip)
+struct LongSums : LongList {
+  float* part = nullptr;
+  size_t bytes = 0;
+};
+
+inline LongSums long_sums_layout(void* workspace, int64_t nnz, int64_t D) {
+  Carver c(workspace);
+  LongSums w;
+  take_long_list(c, nnz, &w);
+  w.part = take_long_chunks<float>(c, nnz, D);
+  w.bytes = c.off;
+  return w;
+}
+
+// What every entry point does before it hands a long-row workspace to its kernels: `need` bytes
+// are there, the base is 16-byte aligned, and the counter (`ctr`, from the layout over this
+// workspace) says "0 rows listed so far".  The refusals carry the caller's name (align_who: the
+// two dispatchers whose alignment message names another function than their size message does).
+inline int begin_long_rows(const char* who, void* workspace, size_t have, size_t need,
+                           unsigned long long* ctr, hipStream_t s, const char* align_who = nullptr) {
+  if (workspace == nullptr || have < need) {
+    set_error(std::string(who) + ": workspace too small");
+    return PSA_ERR_WORKSPACE;
+  }
+  if (!aligned(workspace, 16)) {
+    set_error(std::string(align_who ? align_who : who) + ": workspace must be 16-byte aligned");
+    return PSA_ERR_INVALID_ARG;
+  }
+  return zero_async(ctr, 8, s);
 }
 
 // Lane 0 of a row wave hands a long row to the chunk kernel.

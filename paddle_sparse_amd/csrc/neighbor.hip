@@ -355,8 +355,6 @@ unsigned blocks_for(int64_t n, int per = kThreads) {
   return static_cast<unsigned>(psa::ceil_div(n > 0 ? n : 1, per));
 }
 
-size_t align16(size_t b) { return (b + 15) & ~size_t{15}; }
-
 // hop scratch: e_raw int64[cap] | word int64[cap] | ptr int64[cap+1] | owner int32[cap] | count2ptr scratch
 struct HopWs {
   int64_t *e_raw, *word, *ptr;
@@ -366,22 +364,17 @@ struct HopWs {
 };
 
 size_t hop_layout(int64_t cap, char* base, HopWs* ws) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += align16(bytes);
-    return p;
-  };
+  psa::Carver c(base);
   const size_t n = static_cast<size_t>(cap > 0 ? cap : 1);
   HopWs w;
-  w.e_raw = reinterpret_cast<int64_t*>(take(sizeof(int64_t) * n));
-  w.word = reinterpret_cast<int64_t*>(take(sizeof(int64_t) * n));
-  w.ptr = reinterpret_cast<int64_t*>(take(sizeof(int64_t) * (n + 1)));
-  w.owner = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * n));
+  w.e_raw = c.take<int64_t>(n, 16);
+  w.word = c.take<int64_t>(n, 16);
+  w.ptr = c.take<int64_t>(n + 1, 16);
+  w.owner = c.take<int32_t>(n, 16);
   w.scan_bytes = psa_count2ptr_workspace_bytes(static_cast<int64_t>(n));
-  w.scan = take(w.scan_bytes);
+  w.scan = c.take<char>(w.scan_bytes, 16);
   if (ws) *ws = w;
-  return off;
+  return c.off;
 }
 
 bool in_range(int64_t N) { return N >= 0 && N < (int64_t{1} << 31); }
@@ -391,7 +384,10 @@ bool in_range(int64_t N) { return N >= 0 && N < (int64_t{1} << 31); }
 extern "C" {
 
 size_t psa_neighbor_workspace_bytes(int64_t N) {
-  return in_range(N) ? align16(sizeof(int32_t) * static_cast<size_t>(N > 0 ? N : 1)) : 0;
+  if (!in_range(N)) return 0;
+  psa::Carver c(nullptr);  // one region: the label of every node, int32[N]
+  c.take<int32_t>(static_cast<size_t>(N > 0 ? N : 1), 16);
+  return c.off;
 }
 
 size_t psa_neighbor_hop_workspace_bytes(int64_t slots) {

@@ -492,8 +492,6 @@ rcm_reverse_kernel(const int32_t* __restrict__ order, int64_t N, int64_t* __rest
   if (i < N) perm[i] = order[N - 1 - i];
 }
 
-size_t align256(size_t b) { return (b + 255) & ~size_t{255}; }
-
 // workspace: buf int64[N] (deg, then the frontier's degrees) | seeds int64[N] | fptr int64[N+1] | keys int64[N]
 //            | keys_out int64[N] | pay u32[N] | pay_out u32[N] | rank, claim, order int32[N] | tile_counts
 //            int64[T] | tile_ptr int64[T+1] (T = tiles of nnz candidates) | count2ptr scratch | sort scratch
@@ -510,35 +508,30 @@ int64_t max_tiles(int64_t nnz) { return psa::ceil_div(nnz > 0 ? nnz : 1, kTile);
 size_t rcm_layout(int64_t N, int64_t nnz, char* base, RcmWs* ws) {
   const size_t n = static_cast<size_t>(N > 0 ? N : 1);
   const int64_t T = max_tiles(nnz);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += align256(bytes);
-    return p;
-  };
+  psa::Carver c(base);
   RcmWs w;
-  w.buf = reinterpret_cast<int64_t*>(take(8 * n));
-  w.seeds = reinterpret_cast<int64_t*>(take(8 * n));
-  w.fptr = reinterpret_cast<int64_t*>(take(8 * (n + 1)));
-  w.keys = reinterpret_cast<int64_t*>(take(8 * n));
-  w.keys_out = reinterpret_cast<int64_t*>(take(8 * n));
-  w.pay = reinterpret_cast<uint32_t*>(take(4 * n));
-  w.pay_out = reinterpret_cast<uint32_t*>(take(4 * n));
-  w.rank = reinterpret_cast<int32_t*>(take(4 * n));
-  w.claim = reinterpret_cast<int32_t*>(take(4 * n));
-  w.order = reinterpret_cast<int32_t*>(take(4 * n));
-  w.tile_counts = reinterpret_cast<int64_t*>(take(8 * static_cast<size_t>(T)));
-  w.tile_ptr = reinterpret_cast<int64_t*>(take(8 * static_cast<size_t>(T + 1)));
+  w.buf = c.take<int64_t>(n, 256);
+  w.seeds = c.take<int64_t>(n, 256);
+  w.fptr = c.take<int64_t>(n + 1, 256);
+  w.keys = c.take<int64_t>(n, 256);
+  w.keys_out = c.take<int64_t>(n, 256);
+  w.pay = c.take<uint32_t>(n, 256);
+  w.pay_out = c.take<uint32_t>(n, 256);
+  w.rank = c.take<int32_t>(n, 256);
+  w.claim = c.take<int32_t>(n, 256);
+  w.order = c.take<int32_t>(n, 256);
+  w.tile_counts = c.take<int64_t>(static_cast<size_t>(T), 256);
+  w.tile_ptr = c.take<int64_t>(static_cast<size_t>(T + 1), 256);
   w.scan_bytes = psa_count2ptr_workspace_bytes(N > T ? N : T);
-  w.scan = take(w.scan_bytes);
+  w.scan = c.take<char>(w.scan_bytes, 256);
   // the sort's scratch is not monotonic in n (smaller look-back tiles below 2^20 keys): a level of
   // any size up to N must fit, and psa_sort_pairs_u32 refuses a workspace that is too small
   const int64_t below = (int64_t{1} << 20) - 1;
   const size_t a = psa_index_sort_workspace_bytes(N, 2), b = psa_index_sort_workspace_bytes(N < below ? N : below, 2);
   w.sort_bytes = a > b ? a : b;
-  w.sort = take(w.sort_bytes);
+  w.sort = c.take<char>(w.sort_bytes, 256);
   if (ws) *ws = w;
-  return off;
+  return c.off;
 }
 
 int rcm_args(const char* who, int64_t N, int64_t nnz, const void* workspace, size_t workspace_bytes, RcmWs* ws) {

@@ -344,17 +344,21 @@ softmax_write_kernel(const float* __restrict__ a, const float* __restrict__ b, c
   }
 }
 
-size_t part_bytes(int64_t n, int64_t D) {
-  return psa::align256(sizeof(Part) * static_cast<size_t>(psa::max_long_chunks(n)) * static_cast<size_t>(D));
-}
+// {list, the chunks' partials [chunks, D], the long segments' folded partials [long rows, D]}
+struct LongScratch : psa::LongList {
+  Part* part = nullptr;
+  Part* fin = nullptr;
+  size_t bytes = 0;
+};
 
-size_t fin_bytes(int64_t n, int64_t D) {
-  return psa::align256(sizeof(Part) * static_cast<size_t>(psa::max_long_rows(n)) * static_cast<size_t>(D));
-}
-
-size_t workspace_bytes(int64_t n, int64_t D) {
-  if (n <= psa::kLongRow || D <= 0) return 0;  // no segment can be long
-  return psa::long_list_bytes(n) + part_bytes(n, D) + fin_bytes(n, D);
+LongScratch long_layout(void* workspace, int64_t n, int64_t D) {
+  psa::Carver c(workspace);
+  LongScratch w;
+  psa::take_long_list(c, n, &w);
+  w.part = psa::take_long_chunks<Part>(c, n, D);
+  w.fin = c.take<Part>(static_cast<size_t>(psa::max_long_rows(n)) * static_cast<size_t>(D), 256);
+  w.bytes = c.off;
+  return w;
 }
 
 template <int W, bool BW>
@@ -385,27 +389,14 @@ int run(const char* who, const float* a, const float* b, const int64_t* perm, co
     return PSA_ERR_INVALID_ARG;
   }
   const bool longs = n > psa::kLongRow;
-  unsigned long long* ctr = nullptr;
-  psa::LongEntry* list = nullptr;
-  Part *part = nullptr, *fin = nullptr;
+  LongScratch w;
   if (longs) {
-    if (workspace == nullptr || ws_bytes < workspace_bytes(n, D)) {
-      psa::set_error(std::string(who) + ": workspace too small");
-      return PSA_ERR_WORKSPACE;
-    }
-    if (!psa::aligned(workspace, 16)) {
-      psa::set_error(std::string(who) + ": workspace must be 16-byte aligned");
-      return PSA_ERR_INVALID_ARG;
-    }
-    char* w = static_cast<char*>(workspace);
-    ctr = reinterpret_cast<unsigned long long*>(w);
-    list = reinterpret_cast<psa::LongEntry*>(w + 256);
-    part = reinterpret_cast<Part*>(w + psa::long_list_bytes(n));
-    fin = reinterpret_cast<Part*>(w + psa::long_list_bytes(n) + part_bytes(n, D));
-    PSA_ZERO(ctr, 8, s);
+    w = long_layout(workspace, n, D);
+    const int rc = psa::begin_long_rows(who, workspace, ws_bytes, w.bytes, w.ctr, s);
+    if (rc != PSA_OK) return rc;
     hipLaunchKernelGGL(psa::find_long_rows_kernel,
                        dim3(static_cast<unsigned>(psa::ceil_div(nseg, psa::kFindThreads * psa::kFindIters))),
-                       dim3(psa::kFindThreads), 0, s, indptr, nseg, ctr, list);
+                       dim3(psa::kFindThreads), 0, s, indptr, nseg, w.ctr, w.list);
   }
   const int skip = longs ? 1 : 0;
   switch (W) {
@@ -420,11 +411,11 @@ int run(const char* who, const float* a, const float* b, const int64_t* perm, co
     int64_t rb = psa::ceil_div(psa::max_long_rows(n), kChunkWaves);
     rb = rb > kMaxChunkBlocks ? kMaxChunkBlocks : rb;
     hipLaunchKernelGGL((softmax_chunk_kernel<BW>), dim3(static_cast<unsigned>(cb)), dim3(kThreads), 0, s, a, b, perm,
-                       indptr, n, g, ctr, list, part);
-    hipLaunchKernelGGL((softmax_combine_kernel<BW>), dim3(static_cast<unsigned>(rb)), dim3(kThreads), 0, s, g, ctr,
-                       list, part, fin);
+                       indptr, n, g, w.ctr, w.list, w.part);
+    hipLaunchKernelGGL((softmax_combine_kernel<BW>), dim3(static_cast<unsigned>(rb)), dim3(kThreads), 0, s, g, w.ctr,
+                       w.list, w.part, w.fin);
     hipLaunchKernelGGL((softmax_write_kernel<BW>), dim3(static_cast<unsigned>(cb)), dim3(kThreads), 0, s, a, b, perm,
-                       indptr, n, g, ctr, list, fin, out);
+                       indptr, n, g, w.ctr, w.list, w.fin, out);
   }
   PSA_LAUNCH_CHECK();
   return PSA_OK;
@@ -434,7 +425,10 @@ int run(const char* who, const float* a, const float* b, const int64_t* perm, co
 
 extern "C" {
 
-size_t psa_segment_softmax_workspace_bytes(int64_t n, int64_t D) { return workspace_bytes(n, D); }
+size_t psa_segment_softmax_workspace_bytes(int64_t n, int64_t D) {
+  if (n <= psa::kLongRow || D <= 0) return 0;  // no segment can be long
+  return long_layout(nullptr, n, D).bytes;
+}
 
 int psa_segment_softmax(const float* src, const int64_t* perm, const int64_t* indptr, int64_t nseg, int64_t D,
                         int64_t n, float* out, void* workspace, size_t workspace_bytes, psa_stream_t stream) {

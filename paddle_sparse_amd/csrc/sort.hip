@@ -740,14 +740,21 @@ constexpr int64_t kOsMidBelow = int64_t{1} << 19;    // production: 1024 x 4 bel
 constexpr int64_t kOsHugeFrom = int64_t{1} << 25;    // ... and 1024 x 16 from here
 constexpr int kOsSmallTile = 2048;  // smallest tile any configuration uses (sizes the status words)
 
-size_t os_status_bytes(int64_t n);
-
+// The launch shape of a sort and the regions of its workspace, in their order there.
 struct SortPlan {
   int passes;
   int64_t num_tiles;
   int tiles_per_block;
   int num_blocks;
-  size_t keys_bytes, idx_bytes, counts_bytes, os_bytes, total_bytes;
+  uint64_t* kbuf[2];  // ping-pong keys
+  uint32_t* ibuf[2];  // ping-pong payloads
+  uint32_t* counts;   // [num_blocks][256], then the digit totals [256]
+  // single-sweep area, zeroed as one piece (os_bytes from status on)
+  uint64_t* status;   // look-back words of one pass: [tiles][256], sized for the smallest tile n may get
+  uint32_t* ghist;    // histograms / bases of all passes
+  uint32_t* tickets;  // [kOsMaxPasses]
+  uint32_t* err;      // the fault word
+  size_t os_bytes, total_bytes;
 };
 
 bool single_sweep_variant(int variant) {
@@ -766,15 +773,8 @@ int bits_for(int64_t max_value) {
   return bits;
 }
 
-size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-// look-back words of one pass: [tiles][256] x 8 bytes, sized for the smallest tile n may get
-size_t os_status_bytes(int64_t n) {
-  const int64_t tiles = psa::ceil_div(n > 0 ? n : 1, n < kOsSmallBelow ? kOsSmallTile : kOsTile);
-  return align_up(static_cast<size_t>(tiles) * kRadix * sizeof(uint64_t), 256);
-}
-
-SortPlan make_plan(int64_t n, int64_t max_value) {
+// The one layout of the sort's workspace: over NULL it only sizes it (total_bytes).
+SortPlan make_plan(const void* workspace, int64_t n, int64_t max_value) {
   SortPlan p;
   p.passes = (bits_for(max_value) + 7) / 8;
   p.num_tiles = psa::ceil_div(n > 0 ? n : 1, kTileKeys);
@@ -784,14 +784,18 @@ SortPlan make_plan(int64_t n, int64_t max_value) {
   p.tiles_per_block = static_cast<int>(psa::ceil_div(p.num_tiles, max_blocks));
   if (p.tiles_per_block > 1 && (p.tiles_per_block & 1)) ++p.tiles_per_block;
   p.num_blocks = static_cast<int>(psa::ceil_div(p.num_tiles, p.tiles_per_block));
-  p.keys_bytes = align_up(sizeof(uint64_t) * static_cast<size_t>(n), 256);
-  p.idx_bytes = align_up(sizeof(uint32_t) * static_cast<size_t>(n), 256);
-  p.counts_bytes =
-      align_up(sizeof(uint32_t) * kRadix * (static_cast<size_t>(p.num_blocks) + 8), 256);
-  // single-sweep area: status words, histograms / bases of all passes, tickets, err
-  p.os_bytes = os_status_bytes(n) +
-               align_up(2 * kOsMaxPasses * kRadix * sizeof(uint32_t), 256) + 256;
-  p.total_bytes = 2 * p.keys_bytes + 2 * p.idx_bytes + p.counts_bytes + p.os_bytes;
+  psa::Carver c(const_cast<void*>(workspace));
+  for (uint64_t*& k : p.kbuf) k = c.take<uint64_t>(static_cast<size_t>(n), 256);
+  for (uint32_t*& i : p.ibuf) i = c.take<uint32_t>(static_cast<size_t>(n), 256);
+  p.counts = c.take<uint32_t>(kRadix * (static_cast<size_t>(p.num_blocks) + 8), 256);
+  const size_t os_begin = c.off;
+  const int64_t os_tiles = psa::ceil_div(n > 0 ? n : 1, n < kOsSmallBelow ? kOsSmallTile : kOsTile);
+  p.status = c.take<uint64_t>(static_cast<size_t>(os_tiles) * kRadix, 256);
+  p.ghist = c.take<uint32_t>(2 * kOsMaxPasses * kRadix, 256);
+  p.tickets = c.take<uint32_t>(kOsMaxPasses + 1, 256);  // one 256-byte slot with the fault word
+  p.err = p.tickets ? p.tickets + kOsMaxPasses : nullptr;
+  p.os_bytes = c.off - os_begin;
+  p.total_bytes = c.off;
   return p;
 }
 
@@ -1007,14 +1011,29 @@ small_sort_unique_kernel(const int64_t* __restrict__ row, const int64_t* __restr
   }
 }
 
+// workspace of psa_coalesce_small: the ping-pong keys, then the ping-pong indices
+struct SmallWs {
+  uint64_t* kbuf[2];
+  uint32_t* ibuf[2];
+  size_t bytes;
+};
+
+SmallWs small_layout(void* workspace, int64_t n) {
+  psa::Carver c(workspace);
+  SmallWs w;
+  for (uint64_t*& k : w.kbuf) k = c.take<uint64_t>(static_cast<size_t>(n), 256);
+  for (uint32_t*& i : w.ibuf) i = c.take<uint32_t>(static_cast<size_t>(n), 256);
+  w.bytes = c.off;
+  return w;
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t psa_coalesce_small_workspace_bytes(int64_t n) {
   if (n <= 0) return 256;
-  return 2 * align_up(sizeof(uint64_t) * static_cast<size_t>(n), 256) +
-         2 * align_up(sizeof(uint32_t) * static_cast<size_t>(n), 256);
+  return small_layout(nullptr, n).bytes;
 }
 
 int64_t psa_coalesce_small_max(void) { return 4 * kSmallTile; }
@@ -1026,23 +1045,17 @@ int psa_coalesce_small(const int64_t* row, const int64_t* col, int64_t n, int64_
   PSA_REQUIRE(n > 0 && n <= psa_coalesce_small_max(), "n out of range for the one-workgroup path");
   PSA_REQUIRE(M > 0 && N > 0, "empty matrix");
   PSA_REQUIRE(row && col && out_row && out_col && ptr && perm && count_out, "NULL pointer");
-  if (workspace == nullptr || workspace_bytes < psa_coalesce_small_workspace_bytes(n)) {
+  const SmallWs w = small_layout(workspace, n);
+  if (workspace == nullptr || workspace_bytes < w.bytes) {
     psa::set_error("psa_coalesce_small: workspace too small");
     return PSA_ERR_WORKSPACE;
   }
   PSA_REQUIRE(psa::aligned(workspace, 16), "workspace must be 16-byte aligned");
   int passes = (bits_for(M * N) + 7) / 8;
   if (passes < 1) passes = 1;
-  char* p = static_cast<char*>(workspace);
-  const size_t kb = align_up(sizeof(uint64_t) * static_cast<size_t>(n), 256);
-  const size_t ib = align_up(sizeof(uint32_t) * static_cast<size_t>(n), 256);
-  uint64_t* k0 = reinterpret_cast<uint64_t*>(p);
-  uint64_t* k1 = reinterpret_cast<uint64_t*>(p + kb);
-  uint32_t* i0 = reinterpret_cast<uint32_t*>(p + 2 * kb);
-  uint32_t* i1 = reinterpret_cast<uint32_t*>(p + 2 * kb + ib);
   hipLaunchKernelGGL(small_sort_unique_kernel, dim3(1), dim3(kSmallThreads), 0,
-                     psa::as_stream(stream), row, col, N, n, passes, k0, k1, i0, i1, out_row,
-                     out_col, ptr, perm, count_out);
+                     psa::as_stream(stream), row, col, N, n, passes, w.kbuf[0], w.kbuf[1], w.ibuf[0], w.ibuf[1],
+                     out_row, out_col, ptr, perm, count_out);
   PSA_LAUNCH_CHECK();
   return PSA_OK;
 }
@@ -1061,7 +1074,7 @@ int64_t psa_sort_set_spin_limit(int64_t limit) {
 
 size_t psa_index_sort_workspace_bytes(int64_t n, int64_t max_value) {
   if (n <= 0) return 0;
-  return make_plan(n, max_value).total_bytes;
+  return make_plan(nullptr, n, max_value).total_bytes;
 }
 
 // Shared driver.  perm mode: pay_in == NULL (payload = element index),
@@ -1075,7 +1088,7 @@ static int sort_impl(const char* who, const int64_t* keys, const uint32_t* pay_i
   // bases of every pass already (psa::sort_areas; the coalesce chain does both in its key pass)
   // first_bit > 0: order by the bit field (key >> first_bit) < max_value only;
   // the bits below ride along inside the key (stable, like any other payload)
-  const SortPlan p = make_plan(n, max_value);
+  const SortPlan p = make_plan(workspace, n, max_value);
   if (p.passes == 0) {  // all keys equal: the stable order is the input order
     if (perm_out) {
       hipLaunchKernelGGL(iota_kernel, dim3(static_cast<unsigned>(psa::ceil_div(n, kThreads))),
@@ -1095,12 +1108,7 @@ static int sort_impl(const char* who, const int64_t* keys, const uint32_t* pay_i
     return PSA_ERR_WORKSPACE;
   }
   PSA_REQUIRE(psa::aligned(workspace, 16), "workspace must be 16-byte aligned");
-  char* ws = static_cast<char*>(workspace);
-  uint64_t* kbuf[2] = {reinterpret_cast<uint64_t*>(ws),
-                       reinterpret_cast<uint64_t*>(ws + p.keys_bytes)};
-  uint32_t* ibuf[2] = {reinterpret_cast<uint32_t*>(ws + 2 * p.keys_bytes),
-                       reinterpret_cast<uint32_t*>(ws + 2 * p.keys_bytes + p.idx_bytes)};
-  uint32_t* counts = reinterpret_cast<uint32_t*>(ws + 2 * p.keys_bytes + 2 * p.idx_bytes);
+  uint32_t* counts = p.counts;
   uint32_t* digit_total = counts + static_cast<size_t>(kRadix) * p.num_blocks;
 
   const uint64_t* kin = reinterpret_cast<const uint64_t*>(keys);
@@ -1113,7 +1121,6 @@ static int sort_impl(const char* who, const int64_t* keys, const uint32_t* pay_i
   // 1-4, 7: the three-launch-per-pass family, kept for A/B.
   PSA_REQUIRE(!prepared || variant == 0, "prepared histograms need the single-sweep passes");
   if (single_sweep_variant(variant)) {
-    char* os = ws + 2 * p.keys_bytes + 2 * p.idx_bytes + p.counts_bytes;
     // tile shape: 0 production rule, 5 / 8-11 forced for A/B (tools/sort_tiles.py)
     int os_threads = 512, os_items = 16;
     if (variant == 5) os_threads = 1024, os_items = 8;
@@ -1130,16 +1137,11 @@ static int sort_impl(const char* who, const int64_t* keys, const uint32_t* pay_i
     }
     const int os_tile = os_threads * os_items;
     const size_t os_tiles = static_cast<size_t>(psa::ceil_div(n, os_tile));
-    const size_t status_bytes = os_status_bytes(n);
-    uint64_t* status = reinterpret_cast<uint64_t*>(os);
-    uint32_t* ghist = reinterpret_cast<uint32_t*>(os + status_bytes);
-    uint32_t* tickets = ghist + 2 * kOsMaxPasses * kRadix;  // [kOsMaxPasses] + err word
-    uint32_t* err = tickets + kOsMaxPasses;
     if (!prepared) {
-      PSA_ZERO(os, p.os_bytes, s);
+      PSA_ZERO(p.status, p.os_bytes, s);
       const int hist_blocks = static_cast<int>(psa::ceil_div(n, kThreads * 16) < 2048
                                                    ? psa::ceil_div(n, kThreads * 16) : 2048);
-      hipLaunchKernelGGL(os_hist_kernel, dim3(hist_blocks), block, 0, s, kin, n, p.passes, first_bit, ghist);
+      hipLaunchKernelGGL(os_hist_kernel, dim3(hist_blocks), block, 0, s, kin, n, p.passes, first_bit, p.ghist);
     }
     const dim3 os_grid(static_cast<unsigned>(os_tiles)), os_block(os_threads);
     for (int pass = 0; pass < p.passes; ++pass) {
@@ -1147,12 +1149,12 @@ static int sort_impl(const char* who, const int64_t* keys, const uint32_t* pay_i
       const bool last = pass == p.passes - 1;
       const bool iota_payload = pass == 0 && pay_in == nullptr;
       const bool widen = last && perm_out != nullptr;
-      uint64_t* kout = last ? reinterpret_cast<uint64_t*>(sorted_out) : kbuf[pass & 1];
-      uint32_t* iout = last ? pay_out : ibuf[pass & 1];
+      uint64_t* kout = last ? reinterpret_cast<uint64_t*>(sorted_out) : p.kbuf[pass & 1];
+      uint32_t* iout = last ? pay_out : p.ibuf[pass & 1];
 #define PSA_OS1(P0, L, T, I)                                                                  \
   hipLaunchKernelGGL((os_pass_kernel<P0, L, T, I>), os_grid, os_block, 0, s, kin, iin, kout, \
-                     iout, perm_out, n, shift, pass, ghist + pass * kRadix, status,          \
-                     tickets + pass, err, g_os_spin_limit)
+                     iout, perm_out, n, shift, pass, p.ghist + pass * kRadix, p.status,      \
+                     p.tickets + pass, p.err, g_os_spin_limit)
 #define PSA_OS(P0, L)                                                   \
   do {                                                                  \
     if (os_threads == 512 && os_items == 16) PSA_OS1(P0, L, 512, 16);   \
@@ -1186,8 +1188,8 @@ static int sort_impl(const char* who, const int64_t* keys, const uint32_t* pay_i
                        p.tiles_per_block, p.num_blocks, counts, digit_total);
     hipLaunchKernelGGL(radix_scan_kernel, dim3(kRadix / kWaves), block, 0, s,
                        counts, digit_total, p.num_blocks);
-    uint64_t* kout = last ? reinterpret_cast<uint64_t*>(sorted_out) : kbuf[pass & 1];
-    uint32_t* iout = last ? pay_out : ibuf[pass & 1];
+    uint64_t* kout = last ? reinterpret_cast<uint64_t*>(sorted_out) : p.kbuf[pass & 1];
+    uint32_t* iout = last ? pay_out : p.ibuf[pass & 1];
     if (iota_payload && widen)
       launch_scatter<true, true>(variant, grid, s, kin, iin, kout, iout, perm_out, n, shift, p, counts);
     else if (iota_payload)
@@ -1228,12 +1230,11 @@ namespace psa {
 SortAreas sort_areas(void* workspace, int64_t n, int64_t max_value) {
   SortAreas a{};
   if (n <= 0 || workspace == nullptr) return a;
-  const SortPlan p = make_plan(n, max_value);
+  const SortPlan p = make_plan(workspace, n, max_value);
   a.passes = p.passes;
-  char* os = static_cast<char*>(workspace) + 2 * p.keys_bytes + 2 * p.idx_bytes + p.counts_bytes;
-  a.zero_begin = os;
+  a.zero_begin = p.status;
   a.zero_bytes = p.os_bytes;
-  a.ghist = reinterpret_cast<uint32_t*>(os + os_status_bytes(n));
+  a.ghist = p.ghist;
   return a;
 }
 
@@ -1251,14 +1252,12 @@ int sort_prepared(const int64_t* keys, const uint32_t* pay_in, int64_t n, int64_
 // invalid.  Callers that read a count from the device anyway fold it into that read (chain.hip).
 const uint32_t* sort_fault_word(const void* workspace, int64_t n, int64_t max_value) {
   if (n <= 0 || workspace == nullptr) return nullptr;
-  const SortPlan p = make_plan(n, max_value);
+  const SortPlan p = make_plan(workspace, n, max_value);
   if (p.passes == 0) return nullptr;
   // only the single-sweep passes zero and use the word; behind an A/B variant (1-4, 7) it is
   // untouched scratch (0xff under PSA_POISON_WORKSPACE) and those passes cannot fault
   if (!single_sweep_variant(g_sort_variant & 15)) return nullptr;
-  const char* os = static_cast<const char*>(workspace) + 2 * p.keys_bytes + 2 * p.idx_bytes +
-                   p.counts_bytes;
-  return reinterpret_cast<const uint32_t*>(os + os_status_bytes(n)) + 2 * kOsMaxPasses * kRadix + kOsMaxPasses;
+  return p.err;
 }
 }  // namespace psa
 

@@ -62,7 +62,6 @@ using psa::kLongChunk;
 using psa::kLongRow;
 using psa::LongEntry;
 using psa::max_long_chunks;
-using psa::max_long_rows;
 using psa::push_long_row;
 
 // MASK form of the reduction (grad of the dense operand of spmm_min/max, taken
@@ -887,32 +886,28 @@ spmm_multirow_kernel(const int64_t* __restrict__ rowptr,
 int g_variant = 0;
 
 // Device scratch of the long-row path (carved out of the caller's workspace).
-struct LongScratch {
-  unsigned long long* ctr = nullptr;  // {rows << 32 | chunks}, zeroed every call
-  LongEntry* list = nullptr;
+struct LongScratch : psa::LongList {
   float* part_val = nullptr;
   int64_t* part_arg = nullptr;
+  size_t bytes = 0;
 };
 
-using psa::align256;
-
-size_t long_workspace_bytes(bool minmax, int64_t K, int64_t nnz) {
-  const size_t chunks = static_cast<size_t>(max_long_chunks(nnz));
-  return psa::long_list_bytes(nnz) + align256(chunks * K * sizeof(float)) +
-         (minmax ? align256(chunks * K * sizeof(int64_t)) : 0);
+// {`head` bytes of the caller's own at the base, list, partial values [chunks, K], for min / max
+// the partial winners [chunks, K]}
+LongScratch long_layout(void* workspace, bool minmax, int64_t K, int64_t nnz, size_t head = 0) {
+  psa::Carver c(workspace);
+  LongScratch w;
+  c.take<char>(head, 256);
+  psa::take_long_list(c, nnz, &w);
+  w.part_val = psa::take_long_chunks<float>(c, nnz, K);
+  if (minmax) w.part_arg = psa::take_long_chunks<int64_t>(c, nnz, K);
+  w.bytes = c.off;
+  return w;
 }
 
-LongScratch carve(void* workspace, bool minmax, int64_t K, int64_t nnz) {
-  LongScratch w;
-  char* p = static_cast<char*>(workspace);
-  w.ctr = reinterpret_cast<unsigned long long*>(p);
-  p += 256;
-  w.list = reinterpret_cast<LongEntry*>(p);
-  p += align256(sizeof(LongEntry) * static_cast<size_t>(max_long_rows(nnz)));
-  w.part_val = reinterpret_cast<float*>(p);
-  p += align256(static_cast<size_t>(max_long_chunks(nnz)) * K * sizeof(float));
-  if (minmax) w.part_arg = reinterpret_cast<int64_t*>(p);
-  return w;
+// psa_spmm_minmax_bw_csc keeps arg_out in its row-local form, [M, K] x 2 bytes, in front
+LongScratch minmax_bw_layout(void* workspace, int64_t M, int64_t K, int64_t nnz) {
+  return long_layout(workspace, false, K, nnz > 0 ? nnz : 1, 2 * static_cast<size_t>(M) * K);
 }
 
 // Second and third launch of the long-row path (no-ops when the list is empty).
@@ -1168,7 +1163,7 @@ int psa_csc_edge_tags(const int64_t* rowptr, const int64_t* row_csc, const int64
 
 size_t psa_spmm_minmax_bw_csc_workspace_bytes(int64_t M, int64_t K, int64_t nnz) {
   if (M <= 0 || K <= 0) return 256;
-  return align256(2 * static_cast<size_t>(M) * K) + long_workspace_bytes(false, K, nnz > 0 ? nnz : 1);
+  return minmax_bw_layout(nullptr, M, K, nnz).bytes;
 }
 
 int psa_spmm_minmax_bw_csc(const int64_t* rowptr, const int64_t* colptr,
@@ -1200,15 +1195,12 @@ int psa_spmm_minmax_bw_csc(const int64_t* rowptr, const int64_t* colptr,
               "hot rows go with the two-byte arg_bytes (no arg_out) and 16-byte aligned copies");
   PSA_REQUIRE(grad_value == nullptr || mat != nullptr || nnz == 0, "grad_value needs mat");
   PSA_REQUIRE(max_long_chunks(nnz) < (1ll << 32), "too many chunks");
-  if (workspace == nullptr || workspace_bytes < psa_spmm_minmax_bw_csc_workspace_bytes(M, K, nnz)) {
-    psa::set_error("psa_spmm_minmax_bw_csc: workspace too small");
-    return PSA_ERR_WORKSPACE;
-  }
-  PSA_REQUIRE(psa::aligned(workspace, 16), "workspace must be 16-byte aligned");
   hipStream_t s = psa::as_stream(stream);
+  const LongScratch w = minmax_bw_layout(workspace, M, K, nnz);
+  const int rc = psa::begin_long_rows(__func__, workspace, workspace_bytes,
+                                      psa_spmm_minmax_bw_csc_workspace_bytes(M, K, nnz), w.ctr, s);
+  if (rc != PSA_OK) return rc;
   uint8_t* bytes = static_cast<uint8_t*>(workspace);
-  const LongScratch w = carve(bytes + align256(2 * static_cast<size_t>(M) * K), false, K, nnz > 0 ? nnz : 1);
-  PSA_ZERO(w.ctr, 8, s);
   if (arg_bytes == nullptr && M > 0 && nnz > 0) {  // the forward did not leave the row-local form behind
     const int64_t blocks = psa::ceil_div(M * (K / 4), kThreads);
     PSA_REQUIRE(blocks <= 0x7fffffff, "M*K too large for one launch");
@@ -1268,7 +1260,7 @@ int psa_spmm_minmax_bw_eb(const int64_t* colptr, const int64_t* col_csc, const i
 }
 
 size_t psa_spmm_sum_bw_csc_workspace_bytes(int64_t K, int64_t nnz) {
-  return long_workspace_bytes(false, K > 0 ? K : 1, nnz > 0 ? nnz : 1);
+  return long_layout(nullptr, false, K > 0 ? K : 1, nnz > 0 ? nnz : 1).bytes;
 }
 
 int psa_spmm_sum_bw_csc(const int64_t* colptr, const int64_t* row_csc, const int64_t* csr2csc,
@@ -1290,14 +1282,10 @@ int psa_spmm_sum_bw_csc(const int64_t* colptr, const int64_t* row_csc, const int
   PSA_REQUIRE(nnz == 0 || (row_csc && grad), "NULL pointer");  // csr2csc = NULL: value is in CSC order already
   PSA_REQUIRE(grad_value == nullptr || mat != nullptr || nnz == 0, "grad_value needs mat");
   PSA_REQUIRE(max_long_chunks(nnz) < (1ll << 32), "too many chunks");
-  if (workspace == nullptr || workspace_bytes < psa_spmm_sum_bw_csc_workspace_bytes(K, nnz)) {
-    psa::set_error("psa_spmm_sum_bw_csc: workspace too small");
-    return PSA_ERR_WORKSPACE;
-  }
-  PSA_REQUIRE(psa::aligned(workspace, 16), "workspace must be 16-byte aligned");
   hipStream_t s = psa::as_stream(stream);
-  const LongScratch w = carve(workspace, false, K, nnz > 0 ? nnz : 1);
-  PSA_ZERO(w.ctr, 8, s);
+  const LongScratch w = long_layout(workspace, false, K, nnz > 0 ? nnz : 1);
+  const int rc = psa::begin_long_rows(__func__, workspace, workspace_bytes, w.bytes, w.ctr, s);
+  if (rc != PSA_OK) return rc;
   MaskArgs mask;
   mask.temporal_out = g_variant == 17;
   mask.edge_id = csr2csc;
@@ -1322,7 +1310,7 @@ size_t psa_spmm_workspace_bytes(int reduce, int64_t K, int64_t nnz) {
   if (K <= 0 || nnz <= 0) return 0;
   const bool minmax = reduce == PSA_MIN || reduce == PSA_MAX;
   const size_t eb = K % 4 == 0 ? psa::eb_workspace_bytes(minmax, K, nnz) : 0;
-  const size_t lr = nnz > kLongRow ? long_workspace_bytes(minmax, K, nnz) : 0;  // else no row can be long
+  const size_t lr = nnz > kLongRow ? long_layout(nullptr, minmax, K, nnz).bytes : 0;  // else no row can be long
   return eb > lr ? eb : lr;
 }
 
@@ -1375,14 +1363,10 @@ int spmm_dispatch(int reduce, const int64_t* rowptr, const int64_t* row, const i
   // on its own wave: same results, slow on power-law graphs).
   LongScratch w;
   if (workspace != nullptr && nnz > kLongRow && g_variant != 10) {
-    if (workspace_bytes < long_workspace_bytes(minmax, K, nnz)) {
-      psa::set_error("psa_spmm: workspace too small");
-      return PSA_ERR_WORKSPACE;
-    }
-    PSA_REQUIRE(psa::aligned(workspace, 16), "workspace must be 16-byte aligned");
+    w = long_layout(workspace, minmax, K, nnz);
+    const int rc = psa::begin_long_rows("psa_spmm", workspace, workspace_bytes, w.bytes, w.ctr, s, __func__);
+    if (rc != PSA_OK) return rc;
     PSA_REQUIRE(max_long_chunks(nnz) < (1ll << 32), "too many chunks");
-    w = carve(workspace, minmax, K, nnz);
-    PSA_ZERO(w.ctr, 8, s);
   }
 
 #define PSA_ROW(VEC, LPR, U)                                                 \

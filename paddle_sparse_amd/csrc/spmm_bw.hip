@@ -333,20 +333,15 @@ int psa_spmm_value_bw(int reduce, const int64_t* rowptr, const int64_t* col,
   PSA_REQUIRE(rowptr && col && mat && grad, "NULL pointer");
   const int mean = reduce == PSA_MEAN;
   // long rows: handed to chunk waves when the caller brings the work list
-  unsigned long long* ctr = nullptr;
-  psa::LongEntry* list = nullptr;
+  psa::LongList w;
   if (workspace != nullptr && nnz > psa::kLongRow) {
-    if (workspace_bytes < psa::long_list_bytes(nnz)) {
-      psa::set_error("psa_spmm_value_bw: workspace too small");
-      return PSA_ERR_WORKSPACE;
-    }
-    PSA_REQUIRE(psa::aligned(workspace, 16), "workspace must be 16-byte aligned");
-    ctr = static_cast<unsigned long long*>(workspace);
-    list = reinterpret_cast<psa::LongEntry*>(static_cast<char*>(workspace) + 256);
-    PSA_ZERO(ctr, 8, s);
+    psa::Carver c(workspace);
+    psa::take_long_list(c, nnz, &w);
+    const int rc = psa::begin_long_rows(__func__, workspace, workspace_bytes, c.off, w.ctr, s);
+    if (rc != PSA_OK) return rc;
   }
 #define PSA_VBW(VEC, LPR, U) \
-  return launch_value_bw<VEC, LPR, U>(rowptr, col, mat, grad, out, M, K, mean, ctr, list, s)
+  return launch_value_bw<VEC, LPR, U>(rowptr, col, mat, grad, out, M, K, mean, w.ctr, w.list, s)
   const bool v4 = (K % 4 == 0) && psa::aligned(mat, 16) && psa::aligned(grad, 16);
   if (v4) {
     const int64_t q = K / 4;

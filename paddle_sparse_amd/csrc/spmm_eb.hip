@@ -670,6 +670,26 @@ int scratch_range_len(int64_t K, int E = 4) {
   return d < 128 ? d : 128;
 }
 
+// {COO row ids [nnz] (used when the caller has none), two partial rows per scratch range [slots, K], for min / max
+// their winners [slots, K]}
+struct EbScratch {
+  int64_t* row;
+  float* part_val;
+  int64_t* part_arg;
+  size_t bytes;
+};
+
+EbScratch eb_layout(void* workspace, bool minmax, int64_t K, int64_t nnz, int E) {
+  psa::Carver c(workspace);
+  const size_t slots = 2 * static_cast<size_t>(psa::ceil_div(nnz > 0 ? nnz : 1, scratch_range_len(K, E)));
+  EbScratch w;
+  w.row = c.take<int64_t>(static_cast<size_t>(nnz > 0 ? nnz : 0), 256);
+  w.part_val = c.take<float>(slots * K, 256);
+  w.part_arg = minmax ? c.take<int64_t>(slots * K, 256) : nullptr;
+  w.bytes = c.off;
+  return w;
+}
+
 }  // namespace
 
 namespace psa {
@@ -681,9 +701,7 @@ bool eb_supported(int64_t M, int64_t K, int64_t nnz, int half) {
 
 size_t eb_workspace_bytes(bool minmax, int64_t K, int64_t nnz, int half) {
   if (K <= 0 || nnz <= 0) return 256;
-  const size_t ranges = static_cast<size_t>(ceil_div(nnz, scratch_range_len(K, half ? 8 : 4)));
-  return align256(static_cast<size_t>(nnz) * sizeof(int64_t)) + align256(2 * ranges * K * sizeof(float)) +
-         (minmax ? align256(2 * ranges * K * sizeof(int64_t)) : 0);
+  return eb_layout(nullptr, minmax, K, nnz, half ? 8 : 4).bytes;
 }
 
 int launch_spmm_eb(int red, int mean, const int64_t* rowptr, const int64_t* row,
@@ -703,14 +721,12 @@ int launch_spmm_eb(int red, int mean, const int64_t* rowptr, const int64_t* row,
   PSA_REQUIRE(aligned(workspace, 16), "workspace must be 16-byte aligned");
   const EbPlan plan = eb_plan(K, range_len_override, E);
   PSA_REQUIRE(plan.range_len >= scratch_range_len(K, E), "range too short for the scratch layout");
-  char* p = static_cast<char*>(workspace);
+  const EbScratch w = eb_layout(workspace, minmax, K, nnz, E);
   if (row == nullptr && nnz > 0) {
-    int64_t* built = reinterpret_cast<int64_t*>(p);
-    const int st = psa_ptr2ind(rowptr, M, nnz, built, reinterpret_cast<psa_stream_t>(s));
+    const int st = psa_ptr2ind(rowptr, M, nnz, w.row, reinterpret_cast<psa_stream_t>(s));
     if (st != PSA_OK) return st;
-    row = built;
+    row = w.row;
   }
-  p += align256(static_cast<size_t>(nnz > 0 ? nnz : 0) * sizeof(int64_t));
   EbArgs a;
   a.rowptr = rowptr;
   a.row = row;
@@ -730,10 +746,8 @@ int launch_spmm_eb(int red, int mean, const int64_t* rowptr, const int64_t* row,
   a.nnz = nnz;
   a.range_len = plan.range_len;
   a.num_ranges = ceil_div(nnz, plan.range_len);
-  const size_t slots = 2 * static_cast<size_t>(ceil_div(nnz > 0 ? nnz : 1, scratch_range_len(K, E)));
-  a.part_val = reinterpret_cast<float*>(p);
-  p += align256(slots * K * sizeof(float));
-  a.part_arg = minmax ? reinterpret_cast<int64_t*>(p) : nullptr;
+  a.part_val = w.part_val;
+  a.part_arg = w.part_arg;
   a.fill_blocks = static_cast<unsigned>(ceil_div(M, kFillRows));
   a.mean = mean;
   a.nt_gather = nt_gather ? 1 : 0;

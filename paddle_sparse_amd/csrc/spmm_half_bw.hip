@@ -291,16 +291,7 @@ spmm_half_csc_bw_combine_kernel(int64_t K, const unsigned long long* __restrict_
 }
 
 // scratch of the long-column path: {counter, list of long columns, fp32 partials [chunks, K]}
-struct HalfLong {
-  unsigned long long* ctr = nullptr;
-  psa::LongEntry* list = nullptr;
-  float* part = nullptr;
-};
-
-size_t half_long_bytes(int64_t K, int64_t nnz) {
-  if (K <= 0 || nnz <= psa::kLongRow) return 0;
-  return psa::long_list_bytes(nnz) + psa::align256(sizeof(float) * static_cast<size_t>(psa::max_long_chunks(nnz)) * K);
-}
+using HalfLong = psa::LongSums;
 
 constexpr int kHalfChunkBlocks = 768;  // workgroups in the chunk role (x 4 waves; the fp32 passes use 768 as well)
 
@@ -336,15 +327,10 @@ int dispatch_half_csc_bw(const int64_t* colptr, const int64_t* row_csc, const fl
                          void* workspace, size_t workspace_bytes) {
   HalfLong w;
   if (workspace != nullptr && nnz > psa::kLongRow) {
-    if (workspace_bytes < half_long_bytes(K, nnz)) {
-      psa::set_error("half-width pass over the CSC view: workspace too small");
-      return PSA_ERR_WORKSPACE;
-    }
-    PSA_REQUIRE(psa::aligned(workspace, 16), "workspace must be 16-byte aligned");
-    w.ctr = static_cast<unsigned long long*>(workspace);
-    w.list = reinterpret_cast<psa::LongEntry*>(static_cast<char*>(workspace) + 256);
-    w.part = reinterpret_cast<float*>(static_cast<char*>(workspace) + psa::long_list_bytes(nnz));
-    PSA_ZERO(w.ctr, 8, s);
+    w = psa::long_sums_layout(workspace, nnz, K);
+    const int rc = psa::begin_long_rows("half-width pass over the CSC view", workspace, workspace_bytes, w.bytes, w.ctr,
+                                        s, __func__);
+    if (rc != PSA_OK) return rc;
   }
   const int64_t q = K / 8;
 #define PSA_GO(LPR, U)                                                                                                   \
@@ -401,7 +387,10 @@ extern "C" int psa_spmm_half_sum_bw_csc(int dtype, const int64_t* colptr, const 
                                    nullptr, g_half_variant != 4 && M * K * 2 < (1ll << 32), workspace, workspace_bytes);
 }
 
-extern "C" size_t psa_spmm_half_bw_csc_workspace_bytes(int64_t K, int64_t nnz) { return half_long_bytes(K, nnz); }
+extern "C" size_t psa_spmm_half_bw_csc_workspace_bytes(int64_t K, int64_t nnz) {
+  if (K <= 0 || nnz <= psa::kLongRow) return 0;
+  return psa::long_sums_layout(nullptr, nnz, K).bytes;
+}
 
 extern "C" int psa_spmm_half_minmax_bw_csc(int dtype, const int64_t* colptr, const int64_t* row_csc, const void* tag,
                                            const float* weight_csc, const void* mat, const void* grad,

@@ -224,15 +224,6 @@ spmm_heads_combine_kernel(int64_t D, const unsigned long long* __restrict__ long
   }
 }
 
-size_t spmm_part_bytes(int64_t nnz, int64_t D) {
-  return psa::align256(sizeof(float) * static_cast<size_t>(psa::max_long_chunks(nnz)) * static_cast<size_t>(D));
-}
-
-size_t spmm_workspace_bytes(int64_t nnz, int64_t D) {
-  if (nnz <= psa::kLongRow || D <= 0) return 0;  // no row can be long
-  return psa::long_list_bytes(nnz) + spmm_part_bytes(nnz, D);
-}
-
 template <int VEC, int NT>
 int launch_spmm_heads(const int64_t* rowptr, const int64_t* col, const float* value, const float* mat,
                       const SpmmGeo g, int64_t ntiles, int64_t M, int64_t nnz, float* out, unsigned long long* ctr,
@@ -424,30 +415,13 @@ int launch_sddmm_heads(const int64_t* rowptr, const int64_t* col, const float* x
   return PSA_OK;
 }
 
-// The long-row list at the head of the workspace, its counter zeroed: 0 rows listed so far.
-int take_list(const char* who, void* workspace, size_t have, size_t need, hipStream_t s, unsigned long long** ctr,
-              psa::LongEntry** list) {
-  if (workspace == nullptr || have < need) {
-    psa::set_error(std::string(who) + ": workspace too small");
-    return PSA_ERR_WORKSPACE;
-  }
-  if (!psa::aligned(workspace, 16)) {
-    psa::set_error(std::string(who) + ": workspace must be 16-byte aligned");
-    return PSA_ERR_INVALID_ARG;
-  }
-  *ctr = static_cast<unsigned long long*>(workspace);
-  *list = reinterpret_cast<psa::LongEntry*>(static_cast<char*>(workspace) + 256);
-  PSA_ZERO(*ctr, 8, s);
-  return PSA_OK;
-}
-
 }  // namespace
 
 extern "C" {
 
 size_t psa_spmm_heads_workspace_bytes(int64_t nnz, int64_t H, int64_t F) {
-  if (H <= 0 || F <= 0) return 0;
-  return spmm_workspace_bytes(nnz, H * F);
+  if (H <= 0 || F <= 0 || nnz <= psa::kLongRow) return 0;  // no row can be long
+  return psa::long_sums_layout(nullptr, nnz, H * F).bytes;
 }
 
 int psa_spmm_heads(const int64_t* rowptr, const int64_t* col, const float* value, const float* mat, int64_t M,
@@ -465,14 +439,11 @@ int psa_spmm_heads(const int64_t* rowptr, const int64_t* col, const float* value
     return PSA_OK;
   }
   PSA_REQUIRE(rowptr && col && value && mat, "NULL pointer");
-  unsigned long long* ctr = nullptr;
-  psa::LongEntry* list = nullptr;
-  float* part = nullptr;
+  psa::LongSums w;
   if (nnz > psa::kLongRow) {
-    const int rc = take_list("psa_spmm_heads", workspace, workspace_bytes, spmm_workspace_bytes(nnz, D), s, &ctr,
-                             &list);
+    w = psa::long_sums_layout(workspace, nnz, D);
+    const int rc = psa::begin_long_rows(__func__, workspace, workspace_bytes, w.bytes, w.ctr, s);
     if (rc != PSA_OK) return rc;
-    part = reinterpret_cast<float*>(static_cast<char*>(workspace) + psa::long_list_bytes(nnz));
   }
   const bool v4 = (F % 4 == 0) && psa::aligned(mat, 16) && psa::aligned(out, 16);
   const int vec = v4 ? 4 : 1;
@@ -483,7 +454,7 @@ int psa_spmm_heads(const int64_t* rowptr, const int64_t* col, const float* value
   g.P = pow2_at_least(psa::ceil_div(D, vec), 64, &g.shift);
   const int64_t ntiles = psa::ceil_div(D, static_cast<int64_t>(g.P) * vec);
 #define PSA_SPMM_HEADS(VEC, NT) \
-  return launch_spmm_heads<VEC, NT>(rowptr, col, value, mat, g, ntiles, M, nnz, out, ctr, list, part, s)
+  return launch_spmm_heads<VEC, NT>(rowptr, col, value, mat, g, ntiles, M, nnz, out, w.ctr, w.list, w.part, s)
   if (v4) {
     if (ntiles == 1) PSA_SPMM_HEADS(4, 1);
     if (ntiles == 2) PSA_SPMM_HEADS(4, 2);
@@ -513,11 +484,11 @@ int psa_sddmm_heads(const int64_t* rowptr, const int64_t* col, const float* x, c
     return PSA_OK;
   }
   PSA_REQUIRE(rowptr && col && x && y, "NULL pointer");
-  unsigned long long* ctr = nullptr;
-  psa::LongEntry* list = nullptr;
+  psa::LongList w;
   if (nnz > psa::kLongRow) {
-    const int rc = take_list("psa_sddmm_heads", workspace, workspace_bytes, psa::long_list_bytes(nnz), s, &ctr,
-                             &list);
+    psa::Carver c(workspace);
+    psa::take_long_list(c, nnz, &w);
+    const int rc = psa::begin_long_rows(__func__, workspace, workspace_bytes, c.off, w.ctr, s);
     if (rc != PSA_OK) return rc;
   }
   const bool v4 = (K % 4 == 0) && psa::aligned(x, 16) && psa::aligned(y, 16);
@@ -534,7 +505,7 @@ int psa_sddmm_heads(const int64_t* rowptr, const int64_t* col, const float* x, c
   PSA_REQUIRE(nit <= 0x7fffffff, "H * K too large");
   g.nit = static_cast<int>(nit);
 #define PSA_SDDMM_HEADS(VEC, NR) \
-  return launch_sddmm_heads<VEC, NR>(rowptr, col, x, y, g, M, nnz, out, ctr, list, s)
+  return launch_sddmm_heads<VEC, NR>(rowptr, col, x, y, g, M, nnz, out, w.ctr, w.list, s)
   if (v4) {
     if (nit == 1) PSA_SDDMM_HEADS(4, 1);
     if (nit == 2) PSA_SDDMM_HEADS(4, 2);

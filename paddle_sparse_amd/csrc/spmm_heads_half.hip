@@ -261,20 +261,11 @@ extern "C" int psa_spmm_heads_half(int dtype, const int64_t* rowptr, const int64
     return PSA_OK;
   }
   PSA_REQUIRE(rowptr && col && value && mat, "NULL pointer");
-  unsigned long long* ctr = nullptr;
-  psa::LongEntry* list = nullptr;
-  float* part = nullptr;
+  psa::LongSums w;
   if (nnz > psa::kLongRow) {  // fp32 partials: the workspace of psa_spmm_heads
-    const size_t need = psa_spmm_heads_workspace_bytes(nnz, H, F);
-    if (workspace == nullptr || workspace_bytes < need) {
-      psa::set_error("psa_spmm_heads_half: workspace too small");
-      return PSA_ERR_WORKSPACE;
-    }
-    PSA_REQUIRE(psa::aligned(workspace, 16), "workspace must be 16-byte aligned");
-    ctr = static_cast<unsigned long long*>(workspace);
-    list = reinterpret_cast<psa::LongEntry*>(static_cast<char*>(workspace) + 256);
-    PSA_ZERO(ctr, 8, s);  // 0 rows listed so far
-    part = reinterpret_cast<float*>(static_cast<char*>(workspace) + psa::long_list_bytes(nnz));
+    w = psa::long_sums_layout(workspace, nnz, D);
+    const int rc = psa::begin_long_rows(__func__, workspace, workspace_bytes, w.bytes, w.ctr, s);
+    if (rc != PSA_OK) return rc;
   }
   const bool v8 = (F % 8 == 0) && psa::aligned(mat, 16) && psa::aligned(out, 16);
   const int vec = v8 ? 8 : 1;
@@ -286,7 +277,7 @@ extern "C" int psa_spmm_heads_half(int dtype, const int64_t* rowptr, const int64
   const int64_t ntiles = psa::ceil_div(D, static_cast<int64_t>(g.P) * vec);
 #define PSA_SPMM_HEADS(VEC, NT)                                                                                     \
   return launch_spmm_heads<BF16, VEC, NT>(rowptr, col, value, static_cast<const elem_t*>(mat), g, ntiles, alpha, M, \
-                                          nnz, o, ctr, list, part, s)
+                                          nnz, o, w.ctr, w.list, w.part, s)
   if (v8) {
     if (ntiles == 1) PSA_SPMM_HEADS(8, 1);
     if (ntiles == 2) PSA_SPMM_HEADS(8, 2);

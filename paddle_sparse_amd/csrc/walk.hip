@@ -315,8 +315,6 @@ int grid_for(int64_t n, unsigned* blocks) {
   return 1;
 }
 
-size_t align16(size_t b) { return (b + 15) & ~size_t{15}; }
-
 // workspace: assoc int64[N] | counts int64[S] | in_ptr int64[S+1] | block_counts int64[kBlocks]
 //            | block_ptr int64[kBlocks+1] | count2ptr scratch (max of S and kBlocks)
 struct SaintWs {
@@ -327,22 +325,17 @@ struct SaintWs {
 
 size_t saint_layout(int64_t S, int64_t N, char* base, SaintWs* ws) {
   const int64_t n_scan = S > kBlocks ? S : kBlocks;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += align16(bytes);
-    return p;
-  };
+  psa::Carver c(base);
   SaintWs w;
-  w.assoc = reinterpret_cast<int64_t*>(take(sizeof(int64_t) * static_cast<size_t>(N > 0 ? N : 1)));
-  w.counts = reinterpret_cast<int64_t*>(take(sizeof(int64_t) * static_cast<size_t>(S > 0 ? S : 1)));
-  w.in_ptr = reinterpret_cast<int64_t*>(take(sizeof(int64_t) * static_cast<size_t>(S + 1)));
-  w.block_counts = reinterpret_cast<int64_t*>(take(sizeof(int64_t) * kBlocks));
-  w.block_ptr = reinterpret_cast<int64_t*>(take(sizeof(int64_t) * (kBlocks + 1)));
+  w.assoc = c.take<int64_t>(static_cast<size_t>(N > 0 ? N : 1), 16);
+  w.counts = c.take<int64_t>(static_cast<size_t>(S > 0 ? S : 1), 16);
+  w.in_ptr = c.take<int64_t>(static_cast<size_t>(S + 1), 16);
+  w.block_counts = c.take<int64_t>(kBlocks, 16);
+  w.block_ptr = c.take<int64_t>(kBlocks + 1, 16);
   w.scan_bytes = psa_count2ptr_workspace_bytes(n_scan);
-  w.scan = take(w.scan_bytes);
+  w.scan = c.take<char>(w.scan_bytes, 16);
   if (ws) *ws = w;
-  return off;
+  return c.off;
 }
 
 }  // namespace
