@@ -1260,6 +1260,33 @@ int psa_gat_attention_half_bw_entries(int dtype, const int64_t* rowptr, const in
                                       int64_t nnz, float* p, float* dz, void* workspace, size_t workspace_bytes,
                                       psa_stream_t stream);
 
+/* ---- pair intersection: the sampled sparse x sparse product, its gradients, common neighbours.
+ * (x_ptr int64[x_lists + 1], x_idx, x_val) and (y_ptr int64[y_lists + 1], y_idx, y_val) are two
+ * families of lists in CSR form — a CSR view, or a CSC view read as "the lists of the columns";
+ * every list ascending and free of duplicates.  For every pair p in [0, P):
+ *   out[p] = sum over k in X[pair_x[p]] n Y[pair_y[p]] of x_val * y_val * weight[k]
+ * A NULL value array counts as ones; a NULL weight counts as ones, otherwise it is read at the common
+ * index k (the caller keeps every index value inside it; without a weight index values are only
+ * compared, as int64, and may lie above 2^32).  dtype: PSA_F32, PSA_F64 (values, weight, out) or
+ * PSA_I64, the counting form: x_val, y_val and weight must be NULL and out[p] = |X n Y| as int64.
+ * A stored 0 is not skipped (0 * inf = NaN), as in psa_spmm_heads.  A pair index outside
+ * [0, x_lists) / [0, y_lists) reads nothing and writes 0: the pair list is never taken on trust.
+ * Pairs are independent: any order, duplicates allowed.  out is fully written.  P == 0 launches
+ * nothing; NULL required pointers, negative sizes, another dtype, and values or a weight with
+ * PSA_I64 return PSA_ERR_INVALID_ARG.
+ * The shorter list of a pair is the probe list (tie: X) and each of its elements is binary-searched
+ * in the other.  A probe list of at most 32 elements is run by 8 lanes (8 pairs per wave, lane l
+ * takes elements l, l + 8, ...), a longer one by a whole wave after the wave's short pairs (lane l
+ * takes l, l + 64, ...).  Each lane adds its terms (x_val * y_val) * weight[k] in probe order from 0,
+ * every multiply and add rounded on its own (no FMA); the 8 or 64 partials are folded by the xor
+ * butterfly 1, 2, 4, ...  The sum order is a function of the two list lengths alone.  Every address
+ * is formed in 64-bit arithmetic and the grid strides over the pairs, so P is unbounded.  No
+ * workspace, no atomics, no host read: bitwise reproducible and capturable. */
+int psa_pair_intersect(int dtype, const int64_t* x_ptr, const int64_t* x_idx, const void* x_val, int64_t x_lists,
+                       const int64_t* y_ptr, const int64_t* y_idx, const void* y_val, int64_t y_lists,
+                       const void* weight, const int64_t* pair_x, const int64_t* pair_y, int64_t P, void* out,
+                       psa_stream_t stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -69,6 +69,7 @@ if not _running_the_builder():
         ("sddmm", ("sddmm",)),
         ("attention", ("attention",)),
         ("gat", ("gat_attention",)),
+        ("masked", ("masked_spspmm", "common_neighbors", "triangle_count")),
     )
 
     __all__ = ["__version__"]

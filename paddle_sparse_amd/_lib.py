@@ -231,6 +231,9 @@ SIGNATURES = {
                                                   c_int64, c_float, c_double, c_uint64, c_void_p, c_void_p, c_void_p,
                                                   c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                                   c_void_p, c_size_t, c_void_p]),
+    # (ptr, idx, val, lists) of X and of Y, weight, pair_x, pair_y, P, out
+    "psa_pair_intersect": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                   c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -2501,3 +2501,66 @@ def gat_attention(rowptr: torch.Tensor, col: torch.Tensor, a_row: torch.Tensor, 
     else:
         out = _gat_fw_raw(rowptr, col, a_row, a_col, v, bias, slope, dropout_p, seed)[0]
     return out[:, 0] if flat else out
+
+
+# ---- pair intersection (csrc/intersect.hip) ------------------------------------------
+
+_INTERSECT_DTYPES = (torch.float32, torch.float64, torch.int64)
+
+
+def _list_family(lists, name: str):
+    if not isinstance(lists, (tuple, list)) or len(lists) != 3:
+        raise TypeError(f"{name} must be a (ptr, idx, val or None) triple")
+    ptr, idx, val = lists
+    ptr, idx = _index(ptr, f"{name} ptr"), _index(idx, f"{name} idx")
+    if ptr.numel() < 1:
+        raise ValueError(f"{name} ptr must have at least one element")
+    if val is not None:
+        _gpu(val, f"{name} val")
+    return ptr, idx, val
+
+
+def pair_intersect(x, y, pair_x: torch.Tensor, pair_y: torch.Tensor, weight: Optional[torch.Tensor] = None,
+                   dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """out[p] = sum over k in X[pair_x[p]] n Y[pair_y[p]] of x_val * y_val * weight[k] (psa_pair_intersect).
+    x and y are (ptr, idx, val | None) triples, list families in CSR form: every list ascending and free of
+    duplicates.  A missing val or weight counts as ones; weight is read at the common index, so it must cover
+    every index value.  dtype (default: that of the values and the weight, int64 without any) is float32,
+    float64 or int64, the counting form, which takes neither values nor weight.  A pair index outside its
+    family writes 0.  No scratch, no host read.  The raw op: not differentiable."""
+    x_ptr, x_idx, x_val = _list_family(x, "x")
+    y_ptr, y_idx, y_val = _list_family(y, "y")
+    pair_x, pair_y = _index(pair_x, "pair_x"), _index(pair_y, "pair_y")
+    if pair_x.numel() != pair_y.numel():
+        raise ValueError(f"pair_x and pair_y differ in length ({pair_x.numel()}, {pair_y.numel()})")
+    if weight is not None:
+        _gpu(weight, "weight")
+    given = [(n, t) for n, t in (("x val", x_val), ("y val", y_val), ("weight", weight)) if t is not None]
+    if dtype is None:
+        dtype = given[0][1].dtype if given else torch.int64
+    if dtype not in _INTERSECT_DTYPES:
+        raise TypeError(f"pair_intersect: dtype must be float32, float64 or int64 (got {dtype})")
+    if dtype == torch.int64 and given:
+        raise TypeError("pair_intersect: the counting form (int64) takes no values and no weight")
+    for name, t in given:
+        if t.dtype != dtype:
+            raise TypeError(f"pair_intersect: {name} must be {dtype} (got {t.dtype})")
+        if t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"pair_intersect: {name} must be a contiguous 1-D tensor")
+    for name, val, idx in (("x val", x_val, x_idx), ("y val", y_val, y_idx)):
+        if val is not None and val.numel() != idx.numel():
+            raise ValueError(f"pair_intersect: {name} must have one entry per index ({val.numel()}, {idx.numel()})")
+    dev = pair_x.device
+    for name, t in (("x ptr", x_ptr), ("x idx", x_idx), ("y ptr", y_ptr), ("y idx", y_idx), ("pair_y", pair_y)) \
+            + tuple(given):
+        if t.device != dev:
+            raise ValueError(f"pair_intersect: {name} is on {t.device}, pair_x on {dev}")
+    P = pair_x.numel()
+    out = torch.empty(P, dtype=dtype, device=dev)
+    if P and (x_idx.numel() == 0 or y_idx.numel() == 0):
+        return out.zero_()  # a family without entries has no storage to point at, and no intersection
+    with _on(dev):
+        check(_lib.load().psa_pair_intersect(_DTYPE_ID[dtype], _ptr(x_ptr), _ptr(x_idx), _ptr(x_val), x_ptr.numel() - 1,
+                                             _ptr(y_ptr), _ptr(y_idx), _ptr(y_val), y_ptr.numel() - 1, _ptr(weight),
+                                             _ptr(pair_x), _ptr(pair_y), P, _ptr(out), _stream()))
+    return out
