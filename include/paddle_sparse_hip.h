@@ -866,6 +866,53 @@ int psa_random_walk(const int64_t* rowptr, const int64_t* col, int64_t N, const 
  * 1 / 2 with two walks per lane).  Returns the previous value.  All produce the same bits. */
 int psa_random_walk_set_variant(int variant);
 
+/* ---- edge-weighted sampling: the row CDF, the weighted walk, weighted sample_adj picks.
+ *
+ * row CDF of a CSR matrix with N rows: for every row [s, t) = [rowptr[r], rowptr[r+1]),
+ * cum[s] = w[s] and cum[e] = fl(cum[e-1] + w[e]) in float64, STRICTLY left to right and
+ * afresh in each row: cum equals numpy's cumsum of the row bit for bit, is non-decreasing
+ * for weights >= 0, and cum[e] == cum[e-1] exactly where w[e] == 0.  w, cum: double[nnz]
+ * (distinct buffers).  flags: int64[1], zeroed by the caller; bit 0 = a weight < 0 (-0.0
+ * counts as 0), bit 1 = a NaN or infinite weight, bit 2 = the total of a row of finite
+ * weights overflowed to infinity.  cum is only meaningful when flags stays 0.  One launch,
+ * no workspace, no atomics on floats; capturable. */
+int psa_row_cdf(const int64_t* rowptr, const double* w, int64_t N, double* cum, int64_t* flags,
+                psa_stream_t stream);
+
+/* The weighted pick, on the host (the kernels run the same text, csrc/weighted_pick.h).
+ * cum[0 .. deg) is one row of the row CDF, r the random word of a draw: mix64(stream + t),
+ * the word the uniform draw turns into an index.  total = cum[deg-1]; u = (r >> 11) * 2^-53;
+ * target = u * total, one rounded multiply; the pick is the smallest e with cum[e] > target,
+ * or, when there is none (a subnormal total whose product rounded up to it), the smallest
+ * e with cum[e] == total.  Either way the picked entry has a positive weight.  Returns the
+ * index in [0, deg), or -1 for no pick: deg <= 0, a NULL cum, or a total that is not
+ * positive. */
+int64_t psa_weighted_pick_host(const double* cum, int64_t deg, uint64_t r);
+
+/* The walk of the random-walk sampler above with the step's entry chosen by the weighted
+ * pick: at step l, walk n at node c with d > 0 entries takes entry e = rowptr[c] + pick of
+ * (cum + rowptr[c], d, mix64(stream n + l)) and moves to col[e]; it stays at c when d == 0
+ * or the row's total is zero.  cum: the row CDF of the matrix's weights, or NULL for the
+ * uniform draw, and then out equals the plain random walk's bit for bit.  edge_out:
+ * int64[S, walk_length] or NULL; edge_out[n, l] = e, the storage position of the entry
+ * taken, or -1 where the walk stayed.  flags as for the plain walk.  One launch. */
+int psa_random_walk_weighted(const int64_t* rowptr, const int64_t* col, const double* cum, int64_t N,
+                             const int64_t* start, int64_t S, int64_t walk_length, uint64_t seed, int64_t* out,
+                             int64_t* edge_out, int64_t* flags, psa_stream_t stream);
+
+/* The count and select steps of the sample_adj chain for weighted picks; every other step
+ * of the chain is shared.  counts[i] = deg for num_neighbors < 0; with replace,
+ * num_neighbors when the row's total is > 0 and 0 otherwise.  Slot t of subset row i takes
+ * entry rowptr[idx[i]] + pick of stream i, draw t (entry rowptr[idx[i]] + t for
+ * num_neighbors < 0).  Weighted picks WITHOUT replacement (num_neighbors >= 0 and replace
+ * == 0) are refused with PSA_ERR_INVALID_ARG: successive weighted draws need a per-row
+ * removal structure that these entry points do not have. */
+int psa_sample_count_weighted(const int64_t* rowptr, const double* cum, const int64_t* idx, int64_t S,
+                              int64_t num_neighbors, int replace, int64_t* counts, psa_stream_t stream);
+int psa_sample_select_weighted(const int64_t* rowptr, const double* cum, const int64_t* idx, int64_t S,
+                               const int64_t* out_rowptr, const int64_t* owner, int64_t E, int64_t num_neighbors,
+                               int replace, uint64_t seed, int64_t* e_raw, psa_stream_t stream);
+
 /* saint_subgraph: the subgraph induced by node_idx (int64[S], any order, duplicates
  * allowed).  assoc[node_idx[i]] = i (the last duplicate wins); for every i in order and
  * every entry e of row node_idx[i] with assoc[col[e]] >= 0, the candidate order emits

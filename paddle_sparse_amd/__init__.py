@@ -62,6 +62,7 @@ if not _running_the_builder():
         ("spspmm", ("spspmm",)),
         ("diag", ("remove_diag", "set_diag", "fill_diag", "get_diag")),
         ("rw", ("random_walk",)),
+        ("weighted", ("EdgeCDF",)),
         ("saint", ("saint_subgraph",)),
         ("neighbor", ("neighbor_sample", "NeighborSampler")),
         ("bandwidth", ("reverse_cuthill_mckee",)),

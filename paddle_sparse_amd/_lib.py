@@ -149,6 +149,13 @@ SIGNATURES = {
     "psa_random_walk": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_uint64, c_void_p,
                                 c_void_p, c_void_p]),
     "psa_random_walk_set_variant": (c_int, [c_int]),
+    "psa_row_cdf": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "psa_weighted_pick_host": (c_int64, [c_void_p, c_int64, c_uint64]),
+    "psa_random_walk_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_uint64,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]),
+    "psa_sample_count_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
+    "psa_sample_select_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64,
+                                           c_int, c_uint64, c_void_p, c_void_p]),
     "psa_saint_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "psa_saint_count": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_size_t, c_void_p,
                                 c_void_p]),

@@ -1338,28 +1338,45 @@ def spspmm_expand(rowA, colA, valA, rowptrB, colB, valB, offsets, owner, total: 
 
 
 def sample_adj(rowptr: torch.Tensor, col: torch.Tensor, idx: torch.Tensor, num_neighbors: int,
-               replace: bool = False, seed: int = 0, num_cols: Optional[int] = None
+               replace: bool = False, seed: int = 0, num_cols: Optional[int] = None,
+               cum: Optional[torch.Tensor] = None
                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """paddle_sparse_ops.sample_adj(rowptr, col, idx, num_neighbors, replace)
     (csrc/sample.cpp:8-24, CPU text csrc/cpu/sample_cpu.cpp:9-148) on GPU
     tensors: returns (out_rowptr, out_col, n_id, e_id).  `seed` selects the
     counter-based random stream (see include/paddle_sparse_hip.h); `num_cols`
     (exclusive bound on col, known to the SparseTensor caller) saves the
-    col.max() pass that sizes the relabel scratch."""
+    col.max() pass that sizes the relabel scratch.
+
+    cum (row_cdf of the entries' weights) makes the picks weighted: slot t of subset row i
+    takes the entry the weighted pick of (stream i, draw t) finds in the row's cum, and a row
+    whose total is zero makes no picks.  Only the count and the select step differ; weighted
+    picks without replacement (num_neighbors >= 0, replace False) are not implemented."""
     rowptr, col, idx = _index(rowptr, "rowptr"), _index(col, "col"), _index(idx, "idx")
+    if cum is not None:
+        cum = _cdf(cum, col.numel())
+        if int(num_neighbors) >= 0 and not replace:
+            raise NotImplementedError("sample_adj: weighted picks without replacement are not implemented")
     dev = rowptr.device
     lib = _lib.load()
     S, k, rep, seed = idx.numel(), int(num_neighbors), int(bool(replace)), int(seed) & (2**64 - 1)
     num_nodes = rowptr.numel() - 1
     with _on(dev):
         counts = torch.empty(S, dtype=torch.int64, device=dev)
-        check(lib.psa_sample_count(_ptr(rowptr), _ptr(idx), S, k, rep, _ptr(counts), _stream()))
+        if cum is None:
+            check(lib.psa_sample_count(_ptr(rowptr), _ptr(idx), S, k, rep, _ptr(counts), _stream()))
+        else:
+            check(lib.psa_sample_count_weighted(_ptr(rowptr), _ptr(cum), _ptr(idx), S, k, rep, _ptr(counts), _stream()))
         out_rowptr = count2ptr(counts)
         E = int(out_rowptr[-1].item())
         owner = ptr2ind(out_rowptr, E)
         e_raw = torch.empty(E, dtype=torch.int64, device=dev)
-        check(lib.psa_sample_select(_ptr(rowptr), _ptr(idx), S, _ptr(out_rowptr), _ptr(owner), E,
-                                    k, rep, seed, _ptr(e_raw), _stream()))
+        if cum is None:
+            check(lib.psa_sample_select(_ptr(rowptr), _ptr(idx), S, _ptr(out_rowptr), _ptr(owner), E,
+                                        k, rep, seed, _ptr(e_raw), _stream()))
+        else:
+            check(lib.psa_sample_select_weighted(_ptr(rowptr), _ptr(cum), _ptr(idx), S, _ptr(out_rowptr), _ptr(owner),
+                                                 E, k, rep, seed, _ptr(e_raw), _stream()))
         # node ids live in [0, max(num_rows, num_cols)): col values index newid too
         if num_cols is not None:
             n_scratch = max(num_nodes, int(num_cols))
@@ -1542,6 +1559,76 @@ def random_walk(rowptr: torch.Tensor, col: torch.Tensor, start: torch.Tensor, wa
 def random_walk_set_variant(variant: int) -> int:
     """Bench hook: the store scheme of psa_random_walk (0 = default); returns the previous one."""
     return _lib.load().psa_random_walk_set_variant(int(variant))
+
+
+# ---- edge-weighted sampling (csrc/weighted.hip) -------------------------------------
+
+CDF_NEGATIVE, CDF_NONFINITE, CDF_OVERFLOW = 1, 2, 4
+
+
+def _cdf(cum: torch.Tensor, nnz: int) -> torch.Tensor:
+    _gpu(cum, "cum")
+    if cum.dtype != torch.float64 or cum.dim() != 1 or cum.numel() != nnz:
+        raise ValueError(f"cum must be float64[{nnz}], the row CDF of this matrix")
+    return cum.contiguous()
+
+
+def row_cdf(rowptr: torch.Tensor, weight: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(cum float64[nnz], flags int64[1]): cum is the inclusive prefix sum of weight
+    (float64[nnz]) inside every row, summed strictly left to right in float64, so that it is
+    numpy's cumsum of the row bit for bit.  flags stays on the device (no host read here):
+    CDF_NEGATIVE = a weight < 0, CDF_NONFINITE = a NaN or infinite weight, CDF_OVERFLOW = a
+    row total that overflowed to infinity."""
+    rowptr = _index(rowptr, "rowptr")
+    _gpu(weight, "weight")
+    if weight.dtype != torch.float64 or weight.dim() != 1:
+        raise TypeError("weight must be a 1-D float64 tensor")
+    weight = weight.contiguous()
+    dev = rowptr.device
+    cum = torch.empty_like(weight)
+    flags = torch.zeros(1, dtype=torch.int64, device=dev)
+    with _on(dev):
+        check(_lib.load().psa_row_cdf(_ptr(rowptr), _ptr(weight), rowptr.numel() - 1, _ptr(cum), _ptr(flags),
+                                      _stream()))
+    return cum, flags
+
+
+def weighted_pick_host(cum, r: int) -> int:
+    """The weighted pick of the kernels, run on the host: the index picked in one row's cum
+    (a sequence of floats) by the random word r, or -1 for no pick."""
+    import ctypes
+
+    row = [float(x) for x in cum]
+    arr = (ctypes.c_double * max(len(row), 1))(*row)
+    return int(_lib.load().psa_weighted_pick_host(ctypes.cast(arr, ctypes.c_void_p), len(row), int(r) & (2**64 - 1)))
+
+
+def random_walk_weighted(rowptr: torch.Tensor, col: torch.Tensor, cum: Optional[torch.Tensor], start: torch.Tensor,
+                         walk_length: int, seed: int, return_edge_ids: bool = False):
+    """random_walk with each step's entry drawn in proportion to its weight: cum is row_cdf
+    of the weights (None: the uniform draw, the bits of random_walk).  A walk stays where it
+    is at a node without entries or with a zero total.  With return_edge_ids the result is
+    (walks int64[S, L + 1], e_id int64[S, L]): the storage position of every entry taken, -1
+    where the walk stayed.  Raises IndexError when a start lies outside the matrix (one host
+    read)."""
+    rowptr, col, start = _index(rowptr, "rowptr"), _index(col, "col"), _index(start, "start")
+    if cum is not None:
+        cum = _cdf(cum, col.numel())
+    L = int(walk_length)
+    if L < 0:
+        raise ValueError("walk_length must be >= 0")
+    N, S, dev = rowptr.numel() - 1, start.numel(), rowptr.device
+    out = torch.empty((S, L + 1), dtype=torch.int64, device=dev)
+    e_id = torch.empty((S, L), dtype=torch.int64, device=dev) if return_edge_ids else None
+    if S > 0:
+        flags = torch.zeros(1, dtype=torch.int64, device=dev)
+        with _on(dev):
+            check(_lib.load().psa_random_walk_weighted(_ptr(rowptr), _ptr(col), _ptr(cum), N, _ptr(start), S, L,
+                                                       int(seed) & (2**64 - 1), _ptr(out), _ptr(e_id), _ptr(flags),
+                                                       _stream()))
+            if int(flags.item()) & 1:
+                raise IndexError(f"random_walk: a start node lies outside [0, {N})")
+    return (out, e_id) if return_edge_ids else out
 
 
 SAINT_DUPLICATES, SAINT_UNSORTED = 2, 4

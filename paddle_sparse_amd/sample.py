@@ -38,14 +38,27 @@ def sample(src: SparseTensor, num_neighbors: int, subset: Optional[torch.Tensor]
 
 
 def sample_adj(src: SparseTensor, subset: torch.Tensor, num_neighbors: int, replace: bool = False,
-               seed: Optional[int] = None) -> Tuple[SparseTensor, torch.Tensor]:
+               seed: Optional[int] = None, weighted=False) -> Tuple[SparseTensor, torch.Tensor]:
     """sample.py:30-53: the sampled, relabelled sub-adjacency of `subset`
-    ([len(subset), len(n_id)]) and the node ids n_id its columns refer to."""
+    ([len(subset), len(n_id)]) and the node ids n_id its columns refer to.
+
+    weighted=True (or an EdgeCDF of src, built once) draws every pick in proportion to the
+    entry's value; a row whose values sum to zero then makes no picks, and num_neighbors < 0
+    still takes every entry.  Only picks WITH replacement are weighted: weighted picks
+    without replacement (num_neighbors >= 0, replace=False) raise NotImplementedError before
+    anything is launched, because successive weighted draws need a per-row removal
+    structure.  neighbor_sample has no weighted form either."""
+    from .weighted import resolve
+
+    if weighted is not False and weighted is not None and int(num_neighbors) >= 0 and not replace:
+        raise NotImplementedError("sample_adj: weighted picks without replacement are not implemented; "
+                                  "use replace=True or num_neighbors=-1")
     rowptr, col, value = src.csr()
+    cum = resolve(src, weighted)
     if seed is None:
         seed = int(torch.randint(0, 2**62, (1,)).item())
     out_rowptr, out_col, n_id, e_id = ops.sample_adj(
-        rowptr, col, subset, num_neighbors, replace, seed=seed, num_cols=src.sparse_size(1))
+        rowptr, col, subset, num_neighbors, replace, seed=seed, num_cols=src.sparse_size(1), cum=cum)
     if value is not None:
         value = ops.gather_rows(value, e_id)
     out = SparseTensor(rowptr=out_rowptr, row=None, col=out_col, value=value,
