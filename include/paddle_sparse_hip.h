@@ -1334,6 +1334,83 @@ int psa_pair_intersect(int dtype, const int64_t* x_ptr, const int64_t* x_idx, co
                        const void* weight, const int64_t* pair_x, const int64_t* pair_y, int64_t P, void* out,
                        psa_stream_t stream);
 
+/* ---- ego_k_hop_sample (torch_sparse ego_k_hop_sample_adj, the op behind PyG's
+ * ShaDowKHopSampler): every seed gets a k-hop neighbourhood of its own in a SQUARE N x N CSR
+ * matrix with sorted rows, and the subgraphs induced on the neighbourhoods come back as one
+ * block-diagonal matrix.  Seeds may repeat: every position of `seeds` is an ego of its own.
+ *
+ * Walk list: one global sequence of entries; entries [0, S) are the seeds and entry i belongs
+ * to ego i.  Hop l expands every entry of hop l - 1, duplicates included, and a child belongs
+ * to its parent's ego.  The parent at walk index i that holds node v makes the picks of
+ * psa_sample_count / psa_sample_select for (deg(v), num_neighbors, replace) with the draws of
+ * STREAM i (draw t is randint(seed, i, t, .); Floyd's walk draws randint(seed, i, t,
+ * deg - k + t)), so hop 1 of ego i makes the picks of sample_adj(seeds, k_1, replace, seed)
+ * for row i.  num_neighbors >= 0: the hop has slots = F * num_neighbors, slot f * k + t is
+ * pick t of parent f; a slot past its parent's picks, or of an empty parent, is empty (node
+ * -1), keeps its index and stays empty in later hops: the caller knows the numbering without
+ * a read.  num_neighbors < 0: the slots are the stored entries of the parents' rows in
+ * (parent, storage) order, slots = parent_ptr[F].
+ * Every slot writes node (or -1), ego, and key = ego * N + node; an empty slot writes the key
+ * of its ego's seed, which entry `ego` holds already, so the distinct keys are exactly the
+ * node sets.  There is no relabel map and no workspace.
+ *
+ * The hop loop belongs to the caller (paddle_sparse_amd/ops.py::ego_k_hop_sample):
+ *   psa_ego_init(...)             walk entries [0, S); zeroes the flag word
+ *   per hop with num_neighbors != 0:
+ *     num_neighbors < 0 only:     psa_ego_hop_count -> psa_count2ptr -> parent_ptr,
+ *                                 slots = parent_ptr[F]                          [host read]
+ *     psa_ego_hop_pick(...)       node, ego, key of the hop's slots
+ *   psa_index_sort over all keys (bound S * N), psa_unique_count_after_sort / psa_unique_write:
+ *   n, n_id = key % N, ego_of = key / N                                        [host read]
+ *   psa_ind2ptr(ego_of) -> ptr int64[S + 1]
+ *   psa_ego_induce_count(...)     root[g] = position in n_id of (g, seeds[g]) (-1 for a seed
+ *                                 outside); counts[r] = entries (v, c) of the matrix, v = n_id[r],
+ *                                 with c in the node set of ego_of[r]
+ *   psa_count2ptr(counts) -> rowptr' ; psa_ego_total: state = {rowptr'[n], flags}  [host read]
+ *   psa_ego_induce_write(...)     col_out[q] = ptr[g] + rank of c in ego g's set, edge_out[q] =
+ *                                 the entry's storage position; q ascends in storage order
+ *                                 from rowptr'[r], stored duplicates kept, so the result is
+ *                                 sorted by (row', col') without a sort
+ * Induce passes: the shorter of (row, ego list) probes the longer by binary search, tie: the
+ * row probes.  A probe side of at most T = 32 elements (psa_ego_set_threshold) is run by 8
+ * lanes, 8 rows per wave; longer ones by the whole wave after the wave's short rows.  Both
+ * directions and every T give the same bits.
+ * flags: one int64 on the device; PSA_EGO_SEED_OUTSIDE (such a seed is an empty entry) and
+ * PSA_EGO_COL_OUTSIDE (a stored column outside [0, N): its slot is empty).
+ * Buffers are plain typed arrays of the caller; every entry point takes their element count
+ * and returns PSA_ERR_INVALID_ARG when one is short.  S and slots stay below 2^31 (slots
+ * <= 2^31 - 16), S * N below 2^62, n below 2^31.  Deterministic; no atomics except the flag
+ * word; no launch waits for another workgroup; not capturable in a graph (sizes depend on the
+ * data). */
+#define PSA_EGO_SEED_OUTSIDE 1
+#define PSA_EGO_COL_OUTSIDE 2
+/* Test/bench hook: T, the longest probe side that a group of 8 lanes runs (default 32, at
+ * least 1).  Returns the previous value.  Every value produces the same bits. */
+int psa_ego_set_threshold(int threshold);
+/* node_out int64, ego_out int32, key_out int64: out_count >= S elements each. */
+int psa_ego_init(const int64_t* seeds, int64_t S, int64_t N, int64_t* node_out, int32_t* ego_out, int64_t* key_out,
+                 int64_t out_count, int64_t* flags, psa_stream_t stream);
+/* counts[f] = stored entries of the row of parent_node[f] (0 for an empty entry). */
+int psa_ego_hop_count(const int64_t* rowptr, int64_t N, const int64_t* parent_node, int64_t F, int64_t* counts,
+                      int64_t counts_count, psa_stream_t stream);
+/* parent_node / parent_ego: the F entries of the previous hop, walk indices [begin, begin + F);
+ * parent_ptr int64[F + 1]: read when num_neighbors < 0 only (NULL otherwise). */
+int psa_ego_hop_pick(const int64_t* rowptr, const int64_t* col, int64_t N, const int64_t* seeds, int64_t S,
+                     const int64_t* parent_node, const int32_t* parent_ego, int64_t F, const int64_t* parent_ptr,
+                     int64_t begin, int64_t num_neighbors, int replace, uint64_t seed, int64_t slots,
+                     int64_t* node_out, int32_t* ego_out, int64_t* key_out, int64_t out_count, int64_t* flags,
+                     psa_stream_t stream);
+/* root int64[S], counts int64[n]; col may be NULL for a matrix without entries. */
+int psa_ego_induce_count(const int64_t* rowptr, const int64_t* col, int64_t N, const int64_t* seeds, int64_t S,
+                         const int64_t* n_id, const int64_t* ego_of, const int64_t* ptr, int64_t n, int64_t* root,
+                         int64_t root_count, int64_t* counts, int64_t counts_count, psa_stream_t stream);
+/* state int64[2] = {rowptr_out[n], *flags}: one host read serves both. */
+int psa_ego_total(const int64_t* rowptr_out, int64_t n, const int64_t* flags, int64_t* state, psa_stream_t stream);
+int psa_ego_induce_write(const int64_t* rowptr, const int64_t* col, int64_t N, int64_t S, const int64_t* n_id,
+                         const int64_t* ego_of, const int64_t* ptr, int64_t n, const int64_t* rowptr_out,
+                         int64_t nnz_out, int64_t* col_out, int64_t* edge_out, int64_t out_count,
+                         psa_stream_t stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

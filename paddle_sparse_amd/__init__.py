@@ -65,6 +65,7 @@ if not _running_the_builder():
         ("weighted", ("EdgeCDF",)),
         ("saint", ("saint_subgraph",)),
         ("neighbor", ("neighbor_sample", "NeighborSampler")),
+        ("ego", ("ego_k_hop_sample",)),
         ("bandwidth", ("reverse_cuthill_mckee",)),
         ("softmax", ("softmax",)),
         ("sddmm", ("sddmm",)),

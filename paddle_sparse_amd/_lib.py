@@ -241,6 +241,17 @@ SIGNATURES = {
     # (ptr, idx, val, lists) of X and of Y, weight, pair_x, pair_y, P, out
     "psa_pair_intersect": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                    c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "psa_ego_set_threshold": (c_int, [c_int]),
+    "psa_ego_init": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "psa_ego_hop_count": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "psa_ego_hop_pick": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+                                 c_int64, c_int64, c_int, c_uint64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                 c_void_p, c_void_p]),
+    "psa_ego_induce_count": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                     c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "psa_ego_total": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "psa_ego_induce_write": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                     c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
 }
 
 _lib = None

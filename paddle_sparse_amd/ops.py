@@ -1807,6 +1807,126 @@ def neighbor_sample(rowptr: torch.Tensor, col: torch.Tensor, seeds: torch.Tensor
         return n_id, rowptr_out, col_new, _gather_rows_raw(e_raw, perm), nodes_per_hop, edges_per_hop
 
 
+# ---- ego_k_hop_sample (csrc/ego.hip) ----------------------------------------------------------------
+
+EGO_SEED_OUTSIDE, EGO_COL_OUTSIDE = 1, 2
+EGO_MAX_SLOTS = 2**31 - 16
+
+
+def ego_set_threshold(threshold: int) -> int:
+    """Bench/test hook: T, the longest probe side of an induce row that a group of 8 lanes runs (default 32);
+    returns the previous value.  Every T produces the same bits."""
+    return _lib.load().psa_ego_set_threshold(int(threshold))
+
+
+def ego_k_hop_sample(rowptr: torch.Tensor, col: torch.Tensor, seeds: torch.Tensor, num_neighbors, replace: bool = False,
+                     seed: int = 0, stats: Optional[dict] = None):
+    """Per-seed k-hop ego subgraphs of a square sorted CSR matrix: returns (n_id int64[n],
+    ptr int64[S+1], root int64[S], rowptr' int64[n+1], col' int64[nnz'], e_id int64[nnz']).  seeds int64[S], inside
+    the matrix (IndexError), duplicates allowed: every position is an ego of its own.  num_neighbors: one fan-out
+    >= -1 per hop; -1 takes every entry, 0 ends the sampling.  Hop l expands every walk entry of hop l - 1
+    (duplicates kept); the parent at walk index i draws from stream i of `seed`.  A hop with k >= 0 has (entries of
+    the previous hop) * k slots, known without a read; every hop stays below 2^31 - 16 slots and the walk list as a
+    whole below 2^31 entries (ValueError, before anything is allocated where the fan-outs alone decide it), S * N
+    below 2^62.  Ego g's nodes are n_id[ptr[g]:ptr[g+1]], ascending; root[g] is the position of its seed; the
+    entries are sorted by (row', col') as they are written.
+    Host reads (stats["host_reads"]): one per hop with k < 0 that runs, one for the node count (it carries the
+    sort's fault word) and one for nnz' (it carries the flags): 2 + #{hops run with k < 0}, whatever S; none for
+    S = 0.  stats also receives hops_run and walk_entries.  Not capturable in a graph: the sizes depend on the data."""
+    rowptr, col, seeds = _index(rowptr, "rowptr"), _index(col, "col"), _index(seeds, "seeds")
+    if rowptr.numel() < 1:
+        raise ValueError("rowptr must have at least one element")
+    fanouts = [int(k) for k in num_neighbors]
+    if any(k < -1 for k in fanouts):
+        raise ValueError(f"num_neighbors must be >= -1 (got {fanouts})")
+    N, S, dev = rowptr.numel() - 1, seeds.numel(), rowptr.device
+    if S >= 2**31:
+        raise ValueError(f"ego_k_hop_sample needs fewer than 2^31 seeds (got {S})")
+    if S * N >= 2**62:
+        raise ValueError(f"ego_k_hop_sample: the keys ego * {N} + node of {S} egos do not fit 62 bits")
+    bound = key_bound(S, N, "ego_k_hop_sample")
+
+    def check_slots(hop, slots, total):
+        if slots >= EGO_MAX_SLOTS:
+            raise ValueError(f"ego_k_hop_sample: hop {hop} has {slots} slots, the limit is 2^31 - 16: "
+                             f"to take all entries pass -1, not a large fan-out")
+        if total >= 2**31:
+            raise ValueError(f"ego_k_hop_sample: the walk list reaches {total} entries at hop {hop}, the limit is 2^31")
+
+    # the numbering of the hops with k >= 0 is host arithmetic: refuse before anything is allocated
+    F, total = S, S
+    for hop, k in enumerate(fanouts, 1):
+        if k <= 0 or F == 0:
+            break
+        F *= k
+        total += F
+        check_slots(hop, F, total)
+    count = {"host_reads": 0, "hops_run": 0, "walk_entries": S}
+    i64 = dict(dtype=torch.int64, device=dev)
+    if S == 0:
+        if stats is not None:
+            stats.update(count)
+        return (torch.empty(0, **i64), torch.zeros(1, **i64), torch.empty(0, **i64), torch.zeros(1, **i64),
+                torch.empty(0, **i64), torch.empty(0, **i64))
+    if N == 0:
+        raise IndexError("ego_k_hop_sample: a seed lies outside [0, 0)")
+    lib = _lib.load()
+    rep, seed = int(bool(replace)), int(seed) & (2**64 - 1)
+    with _on(dev):
+        flags = torch.empty(1, **i64)
+        node, ego, key = torch.empty(S, **i64), torch.empty(S, dtype=torch.int32, device=dev), torch.empty(S, **i64)
+        check(lib.psa_ego_init(_ptr(seeds), S, N, _ptr(node), _ptr(ego), _ptr(key), S, _ptr(flags), _stream()))
+        keys, begin, F, total = [key], 0, S, S
+        for hop, k in enumerate(fanouts, 1):
+            if k == 0 or col.numel() == 0:
+                break
+            pptr = None
+            if k < 0:
+                counts = torch.empty(F, **i64)
+                check(lib.psa_ego_hop_count(_ptr(rowptr), N, _ptr(node), F, _ptr(counts), F, _stream()))
+                pptr = count2ptr(counts)
+                slots = int(pptr[-1].item())
+                count["host_reads"] += 1
+                if slots == 0:
+                    break
+            else:
+                slots = F * k
+            total += slots
+            check_slots(hop, slots, total)
+            node2, ego2 = torch.empty(slots, **i64), torch.empty(slots, dtype=torch.int32, device=dev)
+            key2 = torch.empty(slots, **i64)
+            check(lib.psa_ego_hop_pick(_ptr(rowptr), _ptr(col), N, _ptr(seeds), S, _ptr(node), _ptr(ego), F, _ptr(pptr),
+                                       begin, k, rep, seed, slots, _ptr(node2), _ptr(ego2), _ptr(key2), slots,
+                                       _ptr(flags), _stream()))
+            keys.append(key2)
+            begin, F, node, ego = begin + F, slots, node2, ego2
+            count["hops_run"] += 1
+        count["walk_entries"] = total
+        keys = torch.cat(keys) if len(keys) > 1 else keys[0]
+        keys, _, scratch = index_sort(keys, bound, with_sorted_inputs=True, keep_scratch=True)
+        n, _, ego_of, n_id = unique_sorted(keys, N, want_ptr=False, after=scratch)  # the count carries the fault word
+        count["host_reads"] += 1
+        ptr = ind2ptr(ego_of, S)
+        root, counts = torch.empty(S, **i64), torch.empty(n, **i64)
+        check(lib.psa_ego_induce_count(_ptr(rowptr), _ptr(col), N, _ptr(seeds), S, _ptr(n_id), _ptr(ego_of), _ptr(ptr),
+                                       n, _ptr(root), S, _ptr(counts), n, _stream()))
+        rowptr_out = count2ptr(counts)
+        state = torch.empty(2, **i64)
+        check(lib.psa_ego_total(_ptr(rowptr_out), n, _ptr(flags), _ptr(state), _stream()))
+        nnz_out, raised = state.tolist()  # the one read behind the count pass: nnz' and the flags
+        count["host_reads"] += 1
+        if stats is not None:
+            stats.update(count)
+        if raised & EGO_SEED_OUTSIDE:
+            raise IndexError(f"ego_k_hop_sample: a seed lies outside [0, {N})")
+        if raised & EGO_COL_OUTSIDE:
+            raise ValueError(f"ego_k_hop_sample: a stored column lies outside [0, {N})")
+        out = torch.empty((2, nnz_out), **i64)
+        check(lib.psa_ego_induce_write(_ptr(rowptr), _ptr(col), N, S, _ptr(n_id), _ptr(ego_of), _ptr(ptr), n,
+                                       _ptr(rowptr_out), nnz_out, _ptr(out[0]), _ptr(out[1]), nnz_out, _stream()))
+    return n_id, ptr, root, rowptr_out, out[0], out[1]
+
+
 # ---- reverse_cuthill_mckee (csrc/rcm.hip) ---------------------------------------------------------
 
 RCM_DONE, RCM_HANDOVER, RCM_BAD_INPUT = 0, 1, 2
