@@ -900,6 +900,33 @@ int psa_random_walk_weighted(const int64_t* rowptr, const int64_t* col, const do
                              const int64_t* start, int64_t S, int64_t walk_length, uint64_t seed, int64_t* out,
                              int64_t* edge_out, int64_t* flags, psa_stream_t stream);
 
+/* ---- node2vec (p, q) walks: the second-order bias on the walks above, uniform (cum NULL)
+ * or weighted (cum = the row CDF).
+ *
+ * Walk n (stream = rand_stream(seed, n)) at node v at step l, having arrived from t, stays
+ * (node v, edge id -1) when row v is empty or, weighted, its total is not positive.  Else it
+ * makes tries j = 0 .. max_tries - 1: c = stream + l + (j << 32) mod 2^64; the proposal is
+ * the entry e the plain step takes for the word mix64(c) (rowptr[v] + high half of
+ * word * deg, or the weighted pick), x = col[e].  At l == 0 the first proposal is taken.  At
+ * l > 0 its class is 0 if x == t, else 1 if row t stores a column equal to x (lower-bound
+ * binary search in the sorted row, at most 64 halvings), else 2, and it is accepted when
+ * (mix64(c + 2^63) >> 11) < thr<class>.  When no try is accepted the last proposal is
+ * taken.  Then t = v, v = x.  thr0/1/2 <= 2^53 (2^53: always accept; 0: never); the caller
+ * makes them from 1/p, 1, 1/q.  With all three at 2^53 the walks are those of
+ * psa_random_walk_weighted bit for bit.  out, edge_out, flags as there.  One launch, no
+ * workspace, every loop bounded; capturable.  PSA_ERR_INVALID_ARG for a NULL rowptr, start,
+ * out or flags (S > 0), a negative size, max_tries outside [1, 32768] or a threshold
+ * above 2^53. */
+int psa_node2vec_walk(const int64_t* rowptr, const int64_t* col, const double* cum, int64_t N, const int64_t* start,
+                      int64_t S, int64_t walk_length, uint64_t seed, uint64_t thr0, uint64_t thr1, uint64_t thr2,
+                      int max_tries, int64_t* out, int64_t* edge_out, int64_t* flags, psa_stream_t stream);
+/* The same walks run serially on HOST arrays by the same step (csrc/node2vec_step.h): the
+ * step can be checked without a GPU. */
+int psa_node2vec_walk_host(const int64_t* rowptr, const int64_t* col, const double* cum, int64_t N,
+                           const int64_t* start, int64_t S, int64_t walk_length, uint64_t seed, uint64_t thr0,
+                           uint64_t thr1, uint64_t thr2, int max_tries, int64_t* out, int64_t* edge_out,
+                           int64_t* flags);
+
 /* The count and select steps of the sample_adj chain for weighted picks; every other step
  * of the chain is shared.  counts[i] = deg for num_neighbors < 0; with replace,
  * num_neighbors when the row's total is > 0 and 0 otherwise.  Slot t of subset row i takes

@@ -153,6 +153,10 @@ SIGNATURES = {
     "psa_weighted_pick_host": (c_int64, [c_void_p, c_int64, c_uint64]),
     "psa_random_walk_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_uint64,
                                          c_void_p, c_void_p, c_void_p, c_void_p]),
+    "psa_node2vec_walk": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_uint64, c_uint64,
+                                  c_uint64, c_uint64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "psa_node2vec_walk_host": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_uint64,
+                                       c_uint64, c_uint64, c_uint64, c_int, c_void_p, c_void_p, c_void_p]),
     "psa_sample_count_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
     "psa_sample_select_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64,
                                            c_int, c_uint64, c_void_p, c_void_p]),

@@ -1631,6 +1631,71 @@ def random_walk_weighted(rowptr: torch.Tensor, col: torch.Tensor, cum: Optional[
     return (out, e_id) if return_edge_ids else out
 
 
+# ---- node2vec (p, q) walks (csrc/node2vec.hip) ---------------------------------------
+
+NODE2VEC_ONE, NODE2VEC_MAX_TRIES = 2**53, 32768
+
+
+def _node2vec_args(thr, max_tries):
+    thr = tuple(int(t) for t in thr)
+    if len(thr) != 3 or any(t < 0 or t > NODE2VEC_ONE for t in thr):
+        raise ValueError("thr must be three integers in [0, 2^53]")
+    max_tries = int(max_tries)
+    if not 1 <= max_tries <= NODE2VEC_MAX_TRIES:
+        raise ValueError(f"max_tries must lie in [1, {NODE2VEC_MAX_TRIES}]")
+    return thr, max_tries
+
+
+def node2vec_walk(rowptr: torch.Tensor, col: torch.Tensor, cum: Optional[torch.Tensor], start: torch.Tensor,
+                  walk_length: int, seed: int, thr, max_tries: int, return_edge_ids: bool = False):
+    """random_walk_weighted with node2vec's second-order bias: at every step after the first
+    a proposed entry (the plain step's draw) is accepted when a 53-bit random word lies below
+    thr[class], class 0 = back to the previous node t, 1 = a column row t stores, 2 = neither;
+    after max_tries refusals the last proposal is taken (include/paddle_sparse_hip.h states
+    the step in full).  thr: three integers in [0, 2^53]; rw.random_walk makes them from p
+    and q.  cum None: uniform proposals.  Results and IndexError as random_walk_weighted."""
+    rowptr, col, start = _index(rowptr, "rowptr"), _index(col, "col"), _index(start, "start")
+    if cum is not None:
+        cum = _cdf(cum, col.numel())
+    thr, max_tries = _node2vec_args(thr, max_tries)
+    L = int(walk_length)
+    if L < 0:
+        raise ValueError("walk_length must be >= 0")
+    N, S, dev = rowptr.numel() - 1, start.numel(), rowptr.device
+    out = torch.empty((S, L + 1), dtype=torch.int64, device=dev)
+    e_id = torch.empty((S, L), dtype=torch.int64, device=dev) if return_edge_ids else None
+    if S > 0:
+        flags = torch.zeros(1, dtype=torch.int64, device=dev)
+        with _on(dev):
+            check(_lib.load().psa_node2vec_walk(_ptr(rowptr), _ptr(col), _ptr(cum), N, _ptr(start), S, L,
+                                                int(seed) & (2**64 - 1), *thr, max_tries, _ptr(out), _ptr(e_id),
+                                                _ptr(flags), _stream()))
+            if int(flags.item()) & 1:
+                raise IndexError(f"random_walk: a start node lies outside [0, {N})")
+    return (out, e_id) if return_edge_ids else out
+
+
+def node2vec_walk_host(rowptr, col, cum, start, walk_length: int, seed: int, thr, max_tries: int):
+    """node2vec_walk run serially on the host by the kernel's own step (numpy arrays in,
+    (nodes, e_id, flags) numpy out): what the CPU suite holds the restatement to.  flags has
+    bit 0 when a start lies outside the matrix; that walk's rows are left at -7."""
+    import numpy as np
+
+    rowptr = np.ascontiguousarray(rowptr, np.int64)
+    col = np.ascontiguousarray(col, np.int64)
+    start = np.ascontiguousarray(start, np.int64)
+    cum = None if cum is None else np.ascontiguousarray(cum, np.float64)
+    S, L = start.size, int(walk_length)
+    nodes = np.full((S, max(L, 0) + 1), -7, np.int64)
+    e_id = np.full((S, max(L, 0)), -7, np.int64)
+    flags = np.zeros(1, np.int64)
+    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    check(_lib.load().psa_node2vec_walk_host(ptr(rowptr), ptr(col), ptr(cum), rowptr.size - 1, ptr(start), S, L,
+                                             int(seed) & (2**64 - 1), *(int(t) for t in thr), int(max_tries),
+                                             ptr(nodes), ptr(e_id), ptr(flags)))
+    return nodes, e_id, int(flags[0])
+
+
 SAINT_DUPLICATES, SAINT_UNSORTED = 2, 4
 
 
