@@ -927,6 +927,45 @@ int psa_node2vec_walk_host(const int64_t* rowptr, const int64_t* col, const doub
                            uint64_t thr1, uint64_t thr2, int max_tries, int64_t* out, int64_t* edge_out,
                            int64_t* flags);
 
+/* ---- edge lookup and exact negative sampling on a CSR matrix of M rows and N columns sorted
+ * by (row, col); duplicated entries allowed (csrc/negative.hip, csrc/edge_lookup.h).
+ *
+ * psa_edge_lookup: pos_out[q] = the storage position of the FIRST entry (row_q[q], col_q[q]):
+ * a lower-bound binary search for col_q[q] in col[rowptr[r] .. rowptr[r + 1]), at most 64
+ * halvings; -1 when the entry is not stored; -1 with flags bit 0 (value 1) when the pair lies
+ * outside M x N (nothing is read through it).  One launch, one lane per query, no workspace;
+ * flags (int64[1], zeroed by the caller) is only ever OR-ed into; every pos_out[q] is written.
+ *
+ * psa_negative_sample draws S * k samples.  Sample i: stream = rand_stream(seed, i) =
+ * mix64(seed ^ mix64(i)), mix64 the finaliser of splitmix64 (csrc/rng.h).  Try j = 0 ..
+ * max_tries - 1 uses c = stream + j mod 2^64.  The column proposal is cc = high half of the
+ * 128-bit product mix64(c) * N.  With src == NULL (global mode) the row proposal is r = high
+ * half of mix64(c + 2^63) * M; with src (int64[S], structured mode) r = src[i / k].  The try
+ * is accepted iff !(no_self_loops && r == cc) and the search above does not find cc in row r.
+ * The first accepted try is the result: col_out[i] = cc and, in global mode, row_out[i] = r
+ * (row_out is not touched in structured mode and may be NULL).  When no try is accepted the
+ * result is -1 (both outputs) and flags bit 1 (value 2) is raised; with M == 0 or N == 0
+ * every sample fails that way and nothing of the matrix is read.  A given row outside [0, M):
+ * -1 with flags bit 0, nothing read through it.  Draws are with replacement across samples.
+ * One launch, one lane per sample, no workspace, every loop bounded; capturable.
+ *
+ * PSA_ERR_INVALID_ARG: a negative size, k < 1, max_tries outside [1, 32768], S * k
+ * overflowing, no_self_loops with M != N, or (with a non-zero count) a NULL rowptr, query,
+ * output or flags pointer.  A zero count returns PSA_OK and touches nothing.
+ *
+ * The _host forms run the same steps serially on HOST arrays: every result can be checked
+ * without a GPU. */
+int psa_edge_lookup(const int64_t* rowptr, const int64_t* col, int64_t M, int64_t N, const int64_t* row_q,
+                    const int64_t* col_q, int64_t Q, int64_t* pos_out, int64_t* flags, psa_stream_t stream);
+int psa_edge_lookup_host(const int64_t* rowptr, const int64_t* col, int64_t M, int64_t N, const int64_t* row_q,
+                         const int64_t* col_q, int64_t Q, int64_t* pos_out, int64_t* flags);
+int psa_negative_sample(const int64_t* rowptr, const int64_t* col, int64_t M, int64_t N, const int64_t* src, int64_t S,
+                        int64_t k, int no_self_loops, int max_tries, uint64_t seed, int64_t* row_out, int64_t* col_out,
+                        int64_t* flags, psa_stream_t stream);
+int psa_negative_sample_host(const int64_t* rowptr, const int64_t* col, int64_t M, int64_t N, const int64_t* src,
+                             int64_t S, int64_t k, int no_self_loops, int max_tries, uint64_t seed, int64_t* row_out,
+                             int64_t* col_out, int64_t* flags);
+
 /* The count and select steps of the sample_adj chain for weighted picks; every other step
  * of the chain is shared.  counts[i] = deg for num_neighbors < 0; with replace,
  * num_neighbors when the row's total is > 0 and 0 otherwise.  Slot t of subset row i takes

@@ -72,6 +72,7 @@ if not _running_the_builder():
         ("attention", ("attention",)),
         ("gat", ("gat_attention",)),
         ("masked", ("masked_spspmm", "common_neighbors", "triangle_count")),
+        ("negative", ("edge_ids", "has_edge", "negative_sampling", "structured_negative_sampling")),
     )
 
     __all__ = ["__version__"]

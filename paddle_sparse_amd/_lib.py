@@ -157,6 +157,14 @@ SIGNATURES = {
                                   c_uint64, c_uint64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "psa_node2vec_walk_host": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_uint64,
                                        c_uint64, c_uint64, c_uint64, c_int, c_void_p, c_void_p, c_void_p]),
+    "psa_edge_lookup": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                c_void_p]),
+    "psa_edge_lookup_host": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p,
+                                     c_void_p]),
+    "psa_negative_sample": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int,
+                                    c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "psa_negative_sample_host": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int,
+                                         c_int, c_uint64, c_void_p, c_void_p, c_void_p]),
     "psa_sample_count_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
     "psa_sample_select_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64,
                                            c_int, c_uint64, c_void_p, c_void_p]),

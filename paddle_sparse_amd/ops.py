@@ -1696,6 +1696,134 @@ def node2vec_walk_host(rowptr, col, cum, start, walk_length: int, seed: int, thr
     return nodes, e_id, int(flags[0])
 
 
+# ---- edge lookup and negative sampling (csrc/negative.hip) ------------------------------
+
+LOOKUP_RANGE, NEGATIVE_FAILED = 1, 2  # bits of the flags word
+NEGATIVE_MAX_TRIES = 32768
+NEGATIVE_POISON = -(2**62)
+
+
+def _negative_out(out: Optional[torch.Tensor], n: int, dev, name: str) -> torch.Tensor:
+    """The caller's output buffer (int64[n], contiguous, on dev) or a new one, which under the
+    test hook _POISON_WORKSPACE starts as NEGATIVE_POISON (0xff bytes would read as -1, an
+    answer): the kernels write every element."""
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device=dev)
+        return out.fill_(NEGATIVE_POISON) if _POISON_WORKSPACE else out
+    _gpu(out, name)
+    if out.dtype != torch.int64 or out.dim() != 1 or out.numel() != n or not out.is_contiguous() \
+            or out.device != dev:
+        raise ValueError(f"{name} must be a contiguous int64[{n}] tensor on {dev}")
+    return out
+
+
+def edge_lookup(rowptr: torch.Tensor, col: torch.Tensor, N: int, row_q: torch.Tensor, col_q: torch.Tensor,
+                out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(pos int64[Q], flags int64[1]) for a CSR matrix of rowptr.numel() - 1 rows and N columns
+    sorted by (row, col): pos[q] is the storage position of the first entry (row_q[q],
+    col_q[q]), or -1 when it is not stored; a pair outside the matrix gives -1 and sets
+    LOOKUP_RANGE in flags, which stays on the device (no host read here).  One launch; out,
+    when given, receives pos."""
+    rowptr, col = _index(rowptr, "rowptr"), _index(col, "col")
+    row_q, col_q = _index(row_q, "row"), _index(col_q, "col")
+    if row_q.numel() != col_q.numel():
+        raise ValueError(f"row and col differ in length ({row_q.numel()}, {col_q.numel()})")
+    M, N, Q, dev = rowptr.numel() - 1, int(N), row_q.numel(), rowptr.device
+    if M < 0 or N < 0:
+        raise ValueError("rowptr must not be empty and N must be >= 0")
+    pos = _negative_out(out, Q, dev, "out")
+    flags = torch.zeros(1, dtype=torch.int64, device=dev)
+    if Q > 0:
+        with _on(dev):
+            check(_lib.load().psa_edge_lookup(_ptr(rowptr), _ptr(col), M, N, _ptr(row_q), _ptr(col_q), Q, _ptr(pos),
+                                              _ptr(flags), _stream()))
+    return pos, flags
+
+
+def _negative_args(M: int, N: int, k: int, no_self_loops: bool, max_tries: int):
+    k, max_tries = int(k), int(max_tries)
+    if k < 1:
+        raise ValueError("the number of samples per source must be >= 1")
+    if not 1 <= max_tries <= NEGATIVE_MAX_TRIES:
+        raise ValueError(f"max_tries must lie in [1, {NEGATIVE_MAX_TRIES}]")
+    if no_self_loops and M != N:
+        raise ValueError(f"no_self_loops needs a square matrix (got {(M, N)})")
+    return k, max_tries
+
+
+def negative_sample(rowptr: torch.Tensor, col: torch.Tensor, N: int, src: Optional[torch.Tensor], count: int,
+                    no_self_loops: bool, max_tries: int, seed: int, out_row: Optional[torch.Tensor] = None,
+                    out_col: Optional[torch.Tensor] = None):
+    """Pairs that the sorted CSR matrix (rowptr.numel() - 1 rows, N columns) does not store,
+    by at most max_tries proposals per sample from the counter-based stream of `seed`
+    (include/paddle_sparse_hip.h states the step in full).  src None: `count` pairs with the
+    row drawn too; returns (row int64[count], col int64[count], flags).  src int64[S]: `count`
+    columns for every given row; returns (col int64[S * count], flags), sample i belonging to
+    src[i // count].  A sample whose proposals were all refused is -1 and sets
+    NEGATIVE_FAILED; a given row outside the matrix is -1 and sets LOOKUP_RANGE.  flags stays
+    on the device (no host read here).  One launch; out_row / out_col, when given, receive the
+    results."""
+    rowptr, col = _index(rowptr, "rowptr"), _index(col, "col")
+    M, N, dev = rowptr.numel() - 1, int(N), rowptr.device
+    if M < 0 or N < 0:
+        raise ValueError("rowptr must not be empty and N must be >= 0")
+    count = int(count)
+    if src is None:
+        if count < 0:
+            raise ValueError("the number of samples must be >= 0")
+        S, k = count, 1
+        _, max_tries = _negative_args(M, N, 1, no_self_loops, max_tries)
+    else:
+        src = _index(src, "src")
+        S = src.numel()
+        k, max_tries = _negative_args(M, N, count, no_self_loops, max_tries)
+    row = _negative_out(out_row, S * k, dev, "out_row") if src is None else None
+    cols = _negative_out(out_col, S * k, dev, "out_col")
+    flags = torch.zeros(1, dtype=torch.int64, device=dev)
+    if S > 0:
+        with _on(dev):
+            check(_lib.load().psa_negative_sample(_ptr(rowptr), _ptr(col), M, N, _ptr(src), S, k, int(bool(no_self_loops)),
+                                                  max_tries, int(seed) & (2**64 - 1), _ptr(row), _ptr(cols),
+                                                  _ptr(flags), _stream()))
+    return (cols, flags) if src is not None else (row, cols, flags)
+
+
+def edge_lookup_host(rowptr, col, N: int, row_q, col_q):
+    """edge_lookup run serially on the host by the kernel's own step (numpy arrays in, (pos,
+    flags) numpy out): what the CPU suite holds the restatement to.  pos starts at -7: every
+    element is written."""
+    import numpy as np
+
+    rowptr, col = np.ascontiguousarray(rowptr, np.int64), np.ascontiguousarray(col, np.int64)
+    row_q, col_q = np.ascontiguousarray(row_q, np.int64), np.ascontiguousarray(col_q, np.int64)
+    if row_q.shape != col_q.shape or row_q.ndim != 1:
+        raise ValueError("row and col must be 1-D and of one length")
+    pos, flags = np.full(row_q.size, -7, np.int64), np.zeros(1, np.int64)
+    check(_lib.load().psa_edge_lookup_host(rowptr.ctypes.data, col.ctypes.data, rowptr.size - 1, int(N),
+                                           row_q.ctypes.data, col_q.ctypes.data, row_q.size, pos.ctypes.data,
+                                           flags.ctypes.data))
+    return pos, int(flags[0])
+
+
+def negative_sample_host(rowptr, col, N: int, src, count: int, no_self_loops: bool, max_tries: int, seed: int):
+    """negative_sample run serially on the host by the kernel's own step (numpy arrays in,
+    numpy out, flags as an int): (row, col, flags) without src, (col, flags) with it.  The
+    outputs start at -7: every element is written."""
+    import numpy as np
+
+    rowptr, col = np.ascontiguousarray(rowptr, np.int64), np.ascontiguousarray(col, np.int64)
+    src = None if src is None else np.ascontiguousarray(src, np.int64)
+    S, k = (int(count), 1) if src is None else (src.size, int(count))
+    n = max(S, 0) * max(k, 0)
+    row = np.full(n, -7, np.int64) if src is None else None
+    cols, flags = np.full(n, -7, np.int64), np.zeros(1, np.int64)
+    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    check(_lib.load().psa_negative_sample_host(ptr(rowptr), ptr(col), rowptr.size - 1, int(N), ptr(src), S, k,
+                                               int(bool(no_self_loops)), int(max_tries), int(seed) & (2**64 - 1),
+                                               ptr(row), ptr(cols), ptr(flags)))
+    return (cols, int(flags[0])) if src is not None else (row, cols, int(flags[0]))
+
+
 SAINT_DUPLICATES, SAINT_UNSORTED = 2, 4
 
 
