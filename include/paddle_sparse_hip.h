@@ -966,6 +966,45 @@ int psa_negative_sample_host(const int64_t* rowptr, const int64_t* col, int64_t 
                              int64_t S, int64_t k, int no_self_loops, int max_tries, uint64_t seed, int64_t* row_out,
                              int64_t* col_out, int64_t* flags);
 
+/* ---- weakly connected components of an N x N matrix: a lock-free union-find over the stored
+ * entries (csrc/components.hip, csrc/union_find.h).  Every stored entry (u, v) joins u and v,
+ * whatever its direction or value; self loops and duplicates change nothing; the entries need
+ * no order beyond row[] being the expansion of rowptr[].  Three launches on one stream:
+ *
+ *   psa_components_init     parent[v] = c when row v is not empty and its first stored column
+ *                           c = col[rowptr[v]] satisfies 0 <= c < v, else v.  A rowptr[v]
+ *                           outside [0, nnz) reads nothing and gives v.
+ *   psa_components_hook     one lane per entry e: joins row[e] and col[e] in parent (int64[N]
+ *                           as init left it): the larger of the two roots becomes, by one
+ *                           64-bit compare-and-swap, a child of the smaller; a lost race goes
+ *                           on from the value the swap returned.  An entry with an end outside
+ *                           [0, N) joins nothing and raises flags bit 0 (value 1); flags
+ *                           (int64[1], zeroed by the caller) is only ever OR-ed into.
+ *   psa_components_flatten  root[v] = the root of v's tree, which after hook is the smallest
+ *                           node of v's component under any schedule; is_root[v] = (root[v] ==
+ *                           v) as 0 / 1.  parent is compressed along the way.
+ *
+ * The caller ranks the roots: with rank = the exclusive prefix sum of is_root (psa_count2ptr),
+ * rank[N] is the number of components and rank[root[v]] the label of v, the number of
+ * components whose smallest node is below that of v's.  parent, root and is_root are int64[N];
+ * every element is written on every path.  No workspace, no lane waits on another, every loop
+ * is bounded (union_find.h gives the bounds); each grid covers its count, 256 lanes per
+ * workgroup.  The result is deterministic although the order of the links is not.
+ *
+ * PSA_ERR_INVALID_ARG: a negative size, more than 2^31 - 1 workgroups, or (with a non-zero
+ * count: N for init and flatten, nnz for hook) a NULL pointer among those the call uses; col
+ * may be NULL for init when nnz == 0.  A zero count returns PSA_OK and touches nothing.
+ *
+ * psa_components_host runs init, hook and flatten serially on HOST arrays by the same steps:
+ * the result can be checked without a GPU. */
+int psa_components_init(const int64_t* rowptr, const int64_t* col, int64_t N, int64_t nnz, int64_t* parent,
+                        psa_stream_t stream);
+int psa_components_hook(const int64_t* row, const int64_t* col, int64_t nnz, int64_t N, int64_t* parent, int64_t* flags,
+                        psa_stream_t stream);
+int psa_components_flatten(int64_t* parent, int64_t N, int64_t* root, int64_t* is_root, psa_stream_t stream);
+int psa_components_host(const int64_t* rowptr, const int64_t* row, const int64_t* col, int64_t N, int64_t nnz,
+                        int64_t* parent, int64_t* root, int64_t* is_root, int64_t* flags);
+
 /* The count and select steps of the sample_adj chain for weighted picks; every other step
  * of the chain is shared.  counts[i] = deg for num_neighbors < 0; with replace,
  * num_neighbors when the row's total is > 0 and 0 otherwise.  Slot t of subset row i takes

@@ -73,6 +73,7 @@ if not _running_the_builder():
         ("gat", ("gat_attention",)),
         ("masked", ("masked_spspmm", "common_neighbors", "triangle_count")),
         ("negative", ("edge_ids", "has_edge", "negative_sampling", "structured_negative_sampling")),
+        ("components", ("connected_components", "largest_connected_components")),
     )
 
     __all__ = ["__version__"]

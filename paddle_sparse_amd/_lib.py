@@ -165,6 +165,11 @@ SIGNATURES = {
                                     c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "psa_negative_sample_host": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int,
                                          c_int, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "psa_components_init": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "psa_components_hook": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "psa_components_flatten": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "psa_components_host": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                    c_void_p]),
     "psa_sample_count_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p]),
     "psa_sample_select_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64,
                                            c_int, c_uint64, c_void_p, c_void_p]),

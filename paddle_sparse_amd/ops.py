@@ -1824,6 +1824,71 @@ def negative_sample_host(rowptr, col, N: int, src, count: int, no_self_loops: bo
     return (cols, int(flags[0])) if src is not None else (row, cols, int(flags[0]))
 
 
+# ---- connected components (csrc/components.hip) -----------------------------------------
+
+COMPONENTS_RANGE = 1  # bit of the flags word
+
+
+def components_init(rowptr: torch.Tensor, col: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """parent int64[N], N = rowptr.numel() - 1: the first stored column of row v where it is a
+    smaller node, else v.  One launch; out, when given, receives parent."""
+    rowptr, col = _index(rowptr, "rowptr"), _index(col, "col")
+    N, dev = rowptr.numel() - 1, rowptr.device
+    if N < 0:
+        raise ValueError("rowptr must not be empty")
+    parent = _negative_out(out, N, dev, "out")
+    with _on(dev):
+        check(_lib.load().psa_components_init(_ptr(rowptr), _ptr(col), N, col.numel(), _ptr(parent), _stream()))
+    return parent
+
+
+def components_hook(row: torch.Tensor, col: torch.Tensor, parent: torch.Tensor) -> torch.Tensor:
+    """Joins row[e] and col[e] in parent (int64[N] as components_init left it, updated in place)
+    for every entry e; returns flags int64[1], which stays on the device: COMPONENTS_RANGE when
+    an entry had an end outside [0, N) (it joins nothing).  One launch."""
+    row, col = _index(row, "row"), _index(col, "col")
+    if row.numel() != col.numel():
+        raise ValueError(f"row and col differ in length ({row.numel()}, {col.numel()})")
+    N, dev = parent.numel(), row.device
+    _negative_out(parent, N, dev, "parent")
+    flags = torch.zeros(1, dtype=torch.int64, device=dev)
+    with _on(dev):
+        check(_lib.load().psa_components_hook(_ptr(row), _ptr(col), row.numel(), N, _ptr(parent), _ptr(flags),
+                                              _stream()))
+    return flags
+
+
+def components_flatten(parent: torch.Tensor, out_root: Optional[torch.Tensor] = None,
+                       out_is_root: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(root int64[N], is_root int64[N] of 0 / 1) from the parent array that components_hook left
+    (compressed in place along the way).  One launch; out_root / out_is_root, when given, receive
+    the results."""
+    N, dev = parent.numel(), parent.device
+    _negative_out(parent, N, dev, "parent")
+    root = _negative_out(out_root, N, dev, "out_root")
+    is_root = _negative_out(out_is_root, N, dev, "out_is_root")
+    with _on(dev):
+        check(_lib.load().psa_components_flatten(_ptr(parent), N, _ptr(root), _ptr(is_root), _stream()))
+    return root, is_root
+
+
+def components_host(rowptr, row, col):
+    """init, hook and flatten run serially on the host by the kernels' own steps (numpy arrays
+    in, (parent, root, is_root, flags) numpy out, flags as an int): what the CPU suite holds the
+    restatement to.  The outputs start at -7: every element is written."""
+    import numpy as np
+
+    rowptr, row, col = (np.ascontiguousarray(a, np.int64) for a in (rowptr, row, col))
+    if row.shape != col.shape or row.ndim != 1 or rowptr.ndim != 1 or rowptr.size < 1:
+        raise ValueError("row and col must be 1-D and of one length, rowptr 1-D and not empty")
+    N = rowptr.size - 1
+    parent, root, is_root = (np.full(N, -7, np.int64) for _ in range(3))
+    flags = np.zeros(1, np.int64)
+    check(_lib.load().psa_components_host(rowptr.ctypes.data, row.ctypes.data, col.ctypes.data, N, col.size,
+                                          parent.ctypes.data, root.ctypes.data, is_root.ctypes.data, flags.ctypes.data))
+    return parent, root, is_root, int(flags[0])
+
+
 SAINT_DUPLICATES, SAINT_UNSORTED = 2, 4
 
 
