@@ -889,6 +889,25 @@ int psa_row_cdf(const int64_t* rowptr, const double* w, int64_t N, double* cum, 
  * positive. */
 int64_t psa_weighted_pick_host(const double* cum, int64_t deg, uint64_t r);
 
+/* Successive weighted picks WITHOUT replacement from one row of the row CDF, on the host
+ * (the kernels of psa_neighbor_hop_pick_weighted run the same text, csrc/weighted_pick.h).
+ * The positions taken so far, ascending, cut the row into gaps; the mass of a gap is the
+ * difference of cum at its two ends (0.0 below the row's first entry), exactly 0 when it
+ * holds no entry of positive weight.  Draw t: T = the masses summed left to right; the
+ * draws end when T is not positive; the gap is the first whose running sum exceeds
+ * u1 * T, u1 = (words_gap[t] >> 11) * 2^-53 (no word at draw 0: there is one gap; when
+ * the product rounded up to T, the last gap of positive mass); the entry is the smallest e
+ * in the gap with cum[e] > base + u * mass, u from words_entry[t], base = cum just below
+ * the gap (one rounded multiply, one rounded add; when there is none, the smallest e with
+ * cum[e] equal to the gap's last cum).  Draw 0 is psa_weighted_pick_host(cum, deg,
+ * words_entry[0]).  The kernels use words_entry[t] = mix64(stream + t) and words_gap[t] =
+ * mix64(stream + k + t).  out: int64[k], the picks in draw order as indices in [0, deg),
+ * -1 past the last pick.  Returns the number of picks = min(k, entries of positive
+ * weight), all distinct; 0 for a NULL pointer, deg <= 0 or k <= 0.  Row totals so large
+ * that the sum of the gap masses overflows are not supported. */
+int64_t psa_weighted_pick_without_host(const double* cum, int64_t deg, int64_t k, const uint64_t* words_entry,
+                                       const uint64_t* words_gap, int64_t* out);
+
 /* The walk of the random-walk sampler above with the step's entry chosen by the weighted
  * pick: at step l, walk n at node c with d > 0 entries takes entry e = rowptr[c] + pick of
  * (cum + rowptr[c], d, mix64(stream n + l)) and moves to col[e]; it stays at c when d == 0
@@ -1174,6 +1193,23 @@ int psa_neighbor_hop_pick(const int64_t* rowptr, const int64_t* col, int64_t N, 
                           const int64_t* frontier_ptr, int64_t begin, int64_t num_neighbors, int replace,
                           uint64_t seed, int64_t slots, void* workspace, void* hop_workspace,
                           size_t hop_workspace_bytes, int64_t* state, psa_stream_t stream);
+/* psa_neighbor_hop_pick for a hop with num_neighbors >= 1 whose picks are weighted: cum is
+ * the row CDF of the matrix's weights (psa_row_cdf, double[nnz]).  replace = 1: slot t of
+ * the node at local id i takes the entry psa_weighted_pick_host finds with the word
+ * mix64(stream i + t), as weighted sample_adj and the weighted walk do; replace = 0: the
+ * node's picks are those of psa_weighted_pick_without_host with the words of stream i,
+ * slot f * num_neighbors + t holding draw t.  A row makes min(num_neighbors, entries of
+ * positive weight) picks without replacement and none at all when its total is zero; the
+ * remaining slots stay empty.  Same workspaces, state and follow-up
+ * (psa_neighbor_hop_write with the same num_neighbors) as psa_neighbor_hop_pick;
+ * frontier_ptr is not read.  num_neighbors < 0 takes every entry whatever its weight: that
+ * hop goes through psa_neighbor_hop_pick.  Cost without replacement: one thread per
+ * frontier node, O(num_neighbors^2) gap work and num_neighbors binary searches per node. */
+int psa_neighbor_hop_pick_weighted(const int64_t* rowptr, const int64_t* col, const double* cum, int64_t N,
+                                   const int64_t* frontier, int64_t F, const int64_t* frontier_ptr, int64_t begin,
+                                   int64_t num_neighbors, int replace, uint64_t seed, int64_t slots, void* workspace,
+                                   void* hop_workspace, size_t hop_workspace_bytes, int64_t* state,
+                                   psa_stream_t stream);
 /* n_edges, n_new: state[0], state[1] as read after psa_neighbor_hop_pick of the same hop.
  * row_out, col_out and edge_out may be NULL together: only n_id_new and the map are then
  * written (a caller that wants the node set alone). */

@@ -151,6 +151,7 @@ SIGNATURES = {
     "psa_random_walk_set_variant": (c_int, [c_int]),
     "psa_row_cdf": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "psa_weighted_pick_host": (c_int64, [c_void_p, c_int64, c_uint64]),
+    "psa_weighted_pick_without_host": (c_int64, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     "psa_random_walk_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_uint64,
                                          c_void_p, c_void_p, c_void_p, c_void_p]),
     "psa_node2vec_walk": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_uint64, c_uint64,
@@ -195,6 +196,9 @@ SIGNATURES = {
     "psa_neighbor_hop_count": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "psa_neighbor_hop_pick": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int,
                                       c_uint64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "psa_neighbor_hop_pick_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                               c_int64, c_int, c_uint64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p,
+                                               c_void_p]),
     "psa_neighbor_hop_write": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "psa_neighbor_reset": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),

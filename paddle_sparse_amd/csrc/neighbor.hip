@@ -35,6 +35,7 @@
 // No workgroup waits for another one; every loop is bounded by a degree, k or log2(F).
 #include "common.h"
 #include "rng.h"
+#include "weighted_pick.h"
 
 namespace {
 
@@ -504,6 +505,141 @@ int psa_neighbor_reset(const int64_t* ids, int64_t n, int64_t N, const int64_t* 
   if (slots > 0) hop_layout(slots, static_cast<char*>(const_cast<void*>(hop_workspace)), &w);
   hipLaunchKernelGGL(neighbor_reset_kernel, dim3(blocks_for(n + slots)), dim3(kThreads), 0, psa::as_stream(stream),
                      ids, n, N, col, w.e_raw, slots, static_cast<int32_t*>(workspace));
+  PSA_LAUNCH_CHECK();
+  return PSA_OK;
+}
+
+}  // extern "C"
+
+// ---- weighted picks: psa_neighbor_hop_pick with every pick of a hop with
+// num_neighbors >= 0 drawn in proportion to the entries' weights, from the row CDF `cum`.
+// Only the pick kernels differ; claims, flags, the scan and psa_neighbor_hop_write are the
+// chain above.  Without replacement one thread walks one frontier row (weighted_pick.h):
+// slot f * k + t holds draw t, the slots past the row's picks hold -1; up to kWeightedRegs
+// draws the taken positions and the gap masses stay in registers, beyond that the row's
+// slots of e_raw hold the picks in draw order and its slots of `word` (written by the flags
+// pass only afterwards) the ascending view.  Claims run after the walk.
+namespace {
+
+constexpr int kWeightedRegs = 32;   // largest fan-out walked in registers
+constexpr int kWeightedSmall = 16;  // the instantiations for fan-outs up to 16 and up to 8: fewer registers,
+constexpr int kWeightedTiny = 8;    // more waves in flight over the binary searches
+
+struct StreamWords {  // the words of stream st for a fan-out of k: entry(t) is the uniform draw's word
+  uint64_t st, k;
+  __host__ __device__ uint64_t entry(int64_t t) const { return psa::mix64(st + static_cast<uint64_t>(t)); }
+  __host__ __device__ uint64_t gap(int64_t t) const { return psa::mix64(st + k + static_cast<uint64_t>(t)); }
+};
+
+// KMAX > 0: k <= KMAX, walked in registers (a row of 2^31 entries or more takes the memory walk).
+template <int KMAX>
+__global__ void __launch_bounds__(kThreads)
+neighbor_pick_weighted_kernel(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
+                              const double* __restrict__ cum, int64_t N, const int64_t* __restrict__ frontier,
+                              int64_t F, int64_t begin, int64_t k, uint64_t seed, int32_t* __restrict__ local,
+                              int64_t* __restrict__ e_raw, int64_t* __restrict__ sorted,
+                              int64_t* __restrict__ state) {
+  const int64_t f = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  if (f >= F) return;
+  int64_t start, deg;
+  row_of(rowptr, N, frontier[f], &start, &deg);
+  int64_t* mine = e_raw + f * k;
+  const StreamWords words{psa::rand_stream(seed, begin + f), static_cast<uint64_t>(k)};
+  int64_t count = 0;
+  if (deg > 0) {
+    bool walked = false;
+    if constexpr (KMAX > 0) {
+      if (deg <= INT32_MAX) {
+        count = psa::weighted_pick_without_small<KMAX>(cum + start, deg, k, words, mine);
+        walked = true;
+      }
+    }
+    if (!walked) count = psa::weighted_pick_without_large(cum + start, deg, k, words, sorted + f * k, mine);
+  }
+  for (int64_t t = 0; t < k; ++t)
+    mine[t] = t < count ? claim(col, N, start + mine[t], f * k + t, local, state) : -1;
+}
+
+// With replacement: one thread per slot, the pick of the weighted walk and weighted sample_adj.
+__global__ void __launch_bounds__(kThreads)
+neighbor_pick_weighted_slot_kernel(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col,
+                                   const double* __restrict__ cum, int64_t N, const int64_t* __restrict__ frontier,
+                                   int64_t begin, int64_t k, uint64_t seed, int64_t cap, int32_t* __restrict__ local,
+                                   int64_t* __restrict__ e_raw, int64_t* __restrict__ state) {
+  const int64_t p = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
+  if (p >= cap) return;
+  const int64_t f = p / k, t = p - f * k;
+  int64_t start, deg;
+  row_of(rowptr, N, frontier[f], &start, &deg);
+  int64_t e = -1;
+  if (deg > 0) {
+    const int64_t pick =
+        psa::weighted_pick(cum + start, deg, psa::mix64(psa::rand_stream(seed, begin + f) + static_cast<uint64_t>(t)));
+    if (pick >= 0) e = claim(col, N, start + pick, p, local, state);
+  }
+  e_raw[p] = e;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t psa_weighted_pick_without_host(const double* cum, int64_t deg, int64_t k, const uint64_t* words_entry,
+                                       const uint64_t* words_gap, int64_t* out) {
+  if (cum == nullptr || words_entry == nullptr || words_gap == nullptr || out == nullptr || deg <= 0 || k <= 0) return 0;
+  const psa::PickWordArrays words{words_entry, words_gap};
+  int64_t count;
+  if (k <= kWeightedTiny && deg <= INT32_MAX) {
+    count = psa::weighted_pick_without_small<kWeightedTiny>(cum, deg, k, words, out);
+  } else if (k <= kWeightedSmall && deg <= INT32_MAX) {
+    count = psa::weighted_pick_without_small<kWeightedSmall>(cum, deg, k, words, out);
+  } else if (k <= kWeightedRegs && deg <= INT32_MAX) {
+    count = psa::weighted_pick_without_small<kWeightedRegs>(cum, deg, k, words, out);
+  } else {
+    int64_t* sorted = new int64_t[static_cast<size_t>(k)];
+    count = psa::weighted_pick_without_large(cum, deg, k, words, sorted, out);
+    delete[] sorted;
+  }
+  for (int64_t t = count; t < k; ++t) out[t] = -1;
+  return count;
+}
+
+int psa_neighbor_hop_pick_weighted(const int64_t* rowptr, const int64_t* col, const double* cum, int64_t N,
+                                   const int64_t* frontier, int64_t F, const int64_t* frontier_ptr, int64_t begin,
+                                   int64_t num_neighbors, int replace, uint64_t seed, int64_t slots, void* workspace,
+                                   void* hop_workspace, size_t hop_workspace_bytes, int64_t* state,
+                                   psa_stream_t stream) {
+  const int64_t k = num_neighbors;
+  (void)frontier_ptr;  // read by the unweighted entry point when num_neighbors < 0 only
+  PSA_REQUIRE(in_range(N) && F >= 1 && begin >= 0 && begin + F < (int64_t{1} << 31), "frontier out of range");
+  PSA_REQUIRE(slots >= 1 && slots <= kMaxSlots, "slot count out of range");
+  PSA_REQUIRE(k >= 1 && slots == F * k, "num_neighbors must be >= 1 and slots F * num_neighbors");
+  PSA_REQUIRE(rowptr && col && cum && frontier && workspace && state, "NULL pointer");
+  if (hop_workspace == nullptr || hop_workspace_bytes < psa_neighbor_hop_workspace_bytes(slots)) {
+    psa::set_error("psa_neighbor_hop_pick_weighted: hop workspace too small");
+    return PSA_ERR_WORKSPACE;
+  }
+  hipStream_t s = psa::as_stream(stream);
+  auto* local = static_cast<int32_t*>(workspace);
+  HopWs w;
+  hop_layout(slots, static_cast<char*>(hop_workspace), &w);
+#define PSA_PICK_ROWS(KMAX)                                                                                      \
+  hipLaunchKernelGGL(neighbor_pick_weighted_kernel<KMAX>, dim3(blocks_for(F)), dim3(kThreads), 0, s, rowptr, col, \
+                     cum, N, frontier, F, begin, k, seed, local, w.e_raw, w.word, state)
+  if (replace)
+    hipLaunchKernelGGL(neighbor_pick_weighted_slot_kernel, dim3(blocks_for(slots)), dim3(kThreads), 0, s, rowptr, col,
+                       cum, N, frontier, begin, k, seed, slots, local, w.e_raw, state);
+  else if (k <= kWeightedTiny) PSA_PICK_ROWS(kWeightedTiny);
+  else if (k <= kWeightedSmall) PSA_PICK_ROWS(kWeightedSmall);
+  else if (k <= kWeightedRegs) PSA_PICK_ROWS(kWeightedRegs);
+  else PSA_PICK_ROWS(0);
+#undef PSA_PICK_ROWS
+  hipLaunchKernelGGL(neighbor_flags_kernel, dim3(blocks_for(slots)), dim3(kThreads), 0, s, col, w.e_raw, slots, local,
+                     w.word);
+  PSA_LAUNCH_CHECK();
+  const int st = psa_count2ptr(w.word, slots, w.ptr, w.scan, w.scan_bytes, stream);
+  if (st != PSA_OK) return st;
+  hipLaunchKernelGGL(neighbor_state_kernel, dim3(1), dim3(1), 0, s, w.ptr, slots, state);
   PSA_LAUNCH_CHECK();
   return PSA_OK;
 }

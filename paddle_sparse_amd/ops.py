@@ -13,7 +13,7 @@ CPU tensors are rejected: this build has no CPU kernels and never falls back.
 from __future__ import annotations
 
 import os
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -1603,6 +1603,27 @@ def weighted_pick_host(cum, r: int) -> int:
     return int(_lib.load().psa_weighted_pick_host(ctypes.cast(arr, ctypes.c_void_p), len(row), int(r) & (2**64 - 1)))
 
 
+def weighted_pick_without_host(cum, k: int, words_entry, words_gap) -> List[int]:
+    """The weighted picks without replacement of neighbor_sample's kernels, run on the host
+    (DESIGN 3.22): the indices picked in one row's cum (a sequence of floats) by up to k
+    draws, in draw order; draw t uses the random words words_entry[t] and, from draw 1 on,
+    words_gap[t] (sequences of k integers).  min(k, entries of positive weight) picks."""
+    import ctypes
+
+    row = [float(x) for x in cum]
+    k = int(k)
+    if k < 0 or len(words_entry) != k or len(words_gap) != k:
+        raise ValueError("words_entry and words_gap must hold k words each, k >= 0")
+    n = max(k, 1)
+    arr = (ctypes.c_double * max(len(row), 1))(*row)
+    we = (ctypes.c_uint64 * n)(*[int(r) & (2**64 - 1) for r in words_entry])
+    wg = (ctypes.c_uint64 * n)(*[int(r) & (2**64 - 1) for r in words_gap])
+    out = (ctypes.c_int64 * n)(*([-1] * n))
+    as_ptr = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
+    count = int(_lib.load().psa_weighted_pick_without_host(as_ptr(arr), len(row), k, as_ptr(we), as_ptr(wg), as_ptr(out)))
+    return [int(out[t]) for t in range(count)]
+
+
 def random_walk_weighted(rowptr: torch.Tensor, col: torch.Tensor, cum: Optional[torch.Tensor], start: torch.Tensor,
                          walk_length: int, seed: int, return_edge_ids: bool = False):
     """random_walk with each step's entry drawn in proportion to its weight: cum is row_cdf
@@ -1936,7 +1957,7 @@ class NeighborWorkspace:
 
 def neighbor_sample(rowptr: torch.Tensor, col: torch.Tensor, seeds: torch.Tensor, num_neighbors, replace: bool = False,
                     seed: int = 0, workspace: Optional[NeighborWorkspace] = None, stats: Optional[dict] = None,
-                    want_edges: bool = True):
+                    want_edges: bool = True, cum: Optional[torch.Tensor] = None):
     """Multi-hop neighbour sampling of a square sorted CSR matrix: returns
     (n_id int64[n], rowptr' int64[n+1], col' int64[E], e_id int64[E], nodes_per_hop,
     edges_per_hop), the entries sorted (stable) by (row', col').  seeds int64[S], distinct
@@ -1949,8 +1970,24 @@ def neighbor_sample(rowptr: torch.Tensor, col: torch.Tensor, seeds: torch.Tensor
     dict, optional) receives host_reads and hops_run.  workspace: a NeighborWorkspace kept
     between calls.  want_edges=False stops after the node set (the caller induces the
     subgraph): no hop writes its entries and the edge outputs are None.  Not capturable in a graph: the sizes depend on
-    the data.  N, n < 2^31."""
+    the data.  N, n < 2^31.
+    cum (float64[nnz] on the matrix's device, row_cdf of the entries' weights) makes the picks
+    of every hop with a fan-out >= 0 weighted: with replacement slot t is the
+    weighted pick of weighted sample_adj, without replacement the node draws its entries one
+    after the other in proportion to the weights that are left and makes min(k, entries of
+    positive weight) picks.  A fan-out of -1 takes every entry whatever its weight."""
+    if cum is not None:  # checked before anything else looks at a tensor, and before any launch
+        if not isinstance(cum, torch.Tensor):
+            raise TypeError("cum must be a torch.Tensor")
+        if cum.dtype != torch.float64:
+            raise TypeError(f"cum must be float64 (got {cum.dtype})")
+        if not isinstance(col, torch.Tensor) or cum.dim() != 1 or cum.numel() != col.numel():
+            raise ValueError(f"cum must be float64[nnz], the row CDF of this matrix (got shape {tuple(cum.shape)})")
+        if isinstance(rowptr, torch.Tensor) and cum.device != rowptr.device:
+            raise ValueError(f"cum lies on {cum.device}, the matrix on {rowptr.device}")
     rowptr, col, seeds = _index(rowptr, "rowptr"), _index(col, "col"), _index(seeds, "seeds")
+    if cum is not None:
+        cum = cum.contiguous()
     if rowptr.numel() < 1:
         raise ValueError("rowptr must have at least one element")
     fanouts = [int(k) for k in num_neighbors]
@@ -2011,9 +2048,14 @@ def neighbor_sample(rowptr: torch.Tensor, col: torch.Tensor, seeds: torch.Tensor
                     reset()
                     raise ValueError(f"neighbor_sample: a hop of {slots} picks does not fit 2^31")
                 hop_ws = _workspace(nbytes, dev)
-                check(lib.psa_neighbor_hop_pick(_ptr(rowptr), _ptr(col), N, _ptr(frontier), F, _ptr(fptr), begin, k, rep,
-                                                seed, slots, _ptr(ws.buf), _ptr(hop_ws), hop_ws.numel(), _ptr(state),
-                                                _stream()))
+                if cum is not None and k >= 0:
+                    check(lib.psa_neighbor_hop_pick_weighted(_ptr(rowptr), _ptr(col), _ptr(cum), N, _ptr(frontier), F,
+                                                             None, begin, k, rep, seed, slots, _ptr(ws.buf),
+                                                             _ptr(hop_ws), hop_ws.numel(), _ptr(state), _stream()))
+                else:
+                    check(lib.psa_neighbor_hop_pick(_ptr(rowptr), _ptr(col), N, _ptr(frontier), F, _ptr(fptr), begin, k,
+                                                    rep, seed, slots, _ptr(ws.buf), _ptr(hop_ws), hop_ws.numel(),
+                                                    _ptr(state), _stream()))
                 n_edges, n_new, flags = state[:3].tolist()  # the hop's host read
                 count["host_reads"] += 1
                 count["hops_run"] += 1

@@ -1,6 +1,7 @@
 """EdgeCDF — what the edge-weighted samplers read: the prefix sums of a matrix's values
 inside every row (csrc/weighted.hip), built once and held by the user, as a NeighborSampler
-is.  random_walk and sample_adj take one as `weighted=`; `weighted=True` builds one per call.
+is.  random_walk, sample_adj and neighbor_sample take one as `weighted=`; `weighted=True`
+builds one per call (a NeighborSampler: once, at construction).
 
 A weighted pick turns the random word of the uniform draw (csrc/rng.h: stream, draw) into
 u in [0, 1) and looks u * total up in the row's prefix sums, so an entry is taken with
