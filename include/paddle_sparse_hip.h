@@ -1552,6 +1552,75 @@ int psa_ego_induce_write(const int64_t* rowptr, const int64_t* col, int64_t N, i
                          int64_t nnz_out, int64_t* col_out, int64_t* edge_out, int64_t out_count,
                          psa_stream_t stream);
 
+/* ---- temporal_neighbor_sample (torch_sparse hetero_temporal_neighbor_sample on one node type,
+ * the op behind PyG's NeighborLoader(time_attr=...)) ----
+ * Per-seed sampling under a time bound: ego g takes entries with time <= seed_time[g] only,
+ * and the SAMPLED entries of all egos come back as one block-diagonal matrix.
+ *
+ * The matrix comes with a time order (paddle_sparse_amd/temporal.py::EdgeTimeOrder): order
+ * int64[nnz] holds, inside every row, the storage positions ascending by (time, position), and
+ * sorted_time int64[nnz] their times.  The eligible set of a parent holding node v in ego g is
+ * the prefix of row v's segment with sorted_time <= seed_time[g]; c is its length (one
+ * upper-bound search) and a pick is a rank in [0, c), i.e. the entry order[rowptr[v] + rank].
+ *
+ * Walk list, streams and slot numbering are ego_k_hop_sample's (above): psa_ego_init writes
+ * the seeds, hop l expands every entry of hop l - 1, the parent at walk index i draws on
+ * stream i of `seed`, a hop with k >= 0 has F * k slots and a slot past its parent's picks is
+ * empty for good.  Ranks of a parent (csrc/temporal_pick.h):
+ *   k < 0                          0 .. c-1
+ *   strategy 1 (last)              c-1, c-2, ..., c-min(k, c)
+ *   strategy 0, replace            randint(seed, i, t, c) for t < k; none when c == 0
+ *   strategy 0, no replace, c <= k 0 .. c-1
+ *   strategy 0, no replace, c > k  the exact Floyd walk: j = c - k + t, r = randint(seed, i, t,
+ *                                  j + 1), pick = r was picked before ? j : r
+ * Every slot writes node (or -1), ego, key = ego * N + node (an empty slot: the key of its
+ * ego's seed) and edge key = ego * nnz + e (an empty slot: the sentinel S * nnz).
+ *
+ * The hop loop belongs to the caller (paddle_sparse_amd/ops.py::temporal_neighbor_sample):
+ *   psa_ego_init(...)                 walk entries [0, S); zeroes the flag word
+ *   per hop with num_neighbors != 0:
+ *     num_neighbors < 0 only:         psa_temporal_hop_count -> psa_count2ptr -> parent_ptr,
+ *                                     slots = parent_ptr[F]                        [host read]
+ *     psa_temporal_hop_pick(...)      node, ego, key, edge key of the hop's slots
+ *   node keys: psa_index_sort, psa_unique_* -> n, n_id, ego_of; psa_ind2ptr -> ptr  [host read]
+ *   edge keys (one sentinel appended): psa_index_sort, psa_unique_count_after_sort,
+ *   psa_temporal_total: state = {distinct keys, sort fault word, flags}            [host read]
+ *   psa_unique_write -> key_ego, key_edge; the sentinel is the last distinct key: m = count - 1
+ *   psa_temporal_finish(...)          root[g]; row', col', e_id of the m entries, which are in
+ *                                     (row', col') order already; psa_ind2ptr(row') -> rowptr'
+ * flags: one int64 on the device; PSA_EGO_SEED_OUTSIDE, PSA_EGO_COL_OUTSIDE (raised where the
+ * pick reads the column: its slot is empty) and PSA_TEMPORAL_BAD_INDEX (rowptr, order, or the
+ * keys do not describe the matrix: the slot or entry is neutralised, nothing is read or
+ * written out of bounds).  S < 2^31, slots <= 2^31 - 16, S * N and S * nnz below 2^62.
+ * Deterministic; no atomics except the flag word; no launch waits for another workgroup;
+ * grids are sized from the work and not capped; not capturable in a graph. */
+#define PSA_TEMPORAL_BAD_INDEX 4
+/* counts[f] = eligible entries of parent f (0 for an empty entry). */
+int psa_temporal_hop_count(const int64_t* rowptr, const int64_t* sorted_time, int64_t N, int64_t nnz,
+                           const int64_t* seed_time, int64_t S, const int64_t* parent_node, const int32_t* parent_ego,
+                           int64_t F, int64_t* counts, int64_t counts_count, int64_t* flags, psa_stream_t stream);
+/* strategy: 0 uniform, 1 last (replace must be 0).  parent_ptr int64[F + 1]: read when
+ * num_neighbors < 0 only.  The four outputs hold out_count >= slots elements each. */
+int psa_temporal_hop_pick(const int64_t* rowptr, const int64_t* col, const int64_t* order, const int64_t* sorted_time,
+                          int64_t N, int64_t nnz, const int64_t* seeds, const int64_t* seed_time, int64_t S,
+                          const int64_t* parent_node, const int32_t* parent_ego, int64_t F, const int64_t* parent_ptr,
+                          int64_t begin, int64_t num_neighbors, int replace, int strategy, uint64_t seed, int64_t slots,
+                          int64_t* node_out, int32_t* ego_out, int64_t* key_out, int64_t* edge_key_out,
+                          int64_t out_count, int64_t* flags, psa_stream_t stream);
+/* state int64[3] = {count_words[0], count_words[1], *flags}: one host read serves all three. */
+int psa_temporal_total(const int64_t* count_words, const int64_t* flags, int64_t* state, psa_stream_t stream);
+/* key_ego / key_edge int64[m]: the distinct edge keys split by nnz, ascending.  root int64[S];
+ * row_out, col_out, edge_out int64[m]. */
+int psa_temporal_finish(const int64_t* rowptr, const int64_t* col, int64_t N, int64_t nnz, const int64_t* seeds,
+                        int64_t S, const int64_t* key_ego, const int64_t* key_edge, int64_t m, const int64_t* n_id,
+                        const int64_t* ptr, int64_t n, int64_t* root, int64_t root_count, int64_t* row_out,
+                        int64_t* col_out, int64_t* edge_out, int64_t out_count, int64_t* flags, psa_stream_t stream);
+/* Host only (tests): the ranks of one parent on stream `stream_index`, by the text the kernels
+ * run, into ranks[0 .. count); returns count, or -1 for bad arguments or ranks_count < count. */
+int64_t psa_temporal_pick_host(const int64_t* sorted_time, int64_t start, int64_t deg, int64_t bound, int64_t k,
+                               int replace, int strategy, uint64_t seed, int64_t stream_index, int64_t* ranks,
+                               int64_t ranks_count);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

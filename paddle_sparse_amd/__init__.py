@@ -66,6 +66,7 @@ if not _running_the_builder():
         ("saint", ("saint_subgraph",)),
         ("neighbor", ("neighbor_sample", "NeighborSampler")),
         ("ego", ("ego_k_hop_sample",)),
+        ("temporal", ("EdgeTimeOrder", "temporal_neighbor_sample")),
         ("bandwidth", ("reverse_cuthill_mckee",)),
         ("softmax", ("softmax",)),
         ("sddmm", ("sddmm",)),

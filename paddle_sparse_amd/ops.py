@@ -2227,6 +2227,192 @@ def ego_k_hop_sample(rowptr: torch.Tensor, col: torch.Tensor, seeds: torch.Tenso
     return n_id, ptr, root, rowptr_out, out[0], out[1]
 
 
+# ---- temporal_neighbor_sample (csrc/temporal.hip) ---------------------------------------------------
+
+TEMPORAL_BAD_INDEX = 4
+TEMPORAL_STRATEGY = {"uniform": 0, "last": 1}
+
+
+def edge_time_order(rowptr: torch.Tensor, time: torch.Tensor, lo: int, hi: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(order int64[nnz], sorted_time int64[nnz]) of EdgeTimeOrder: inside every row the storage positions
+    ascending by (time, position), and their times.  time int64[nnz] in storage order with lo <= time <= hi
+    (hi - lo < 2^62).  Two stable sorts, by time - lo and then by row, and two gathers; both fault words are
+    read (check=True)."""
+    rowptr, time = _index(rowptr, "rowptr"), _index(time, "time")
+    N, nnz = rowptr.numel() - 1, time.numel()
+    if nnz == 0:
+        return time.clone(), time.clone()
+    _, by_time = index_sort(time - lo, hi - lo + 1, check=True)
+    rows = _gather_rows_raw(ptr2ind(rowptr, nnz), by_time)
+    _, by_row = index_sort(rows, N, check=True)
+    order = _gather_rows_raw(by_time, by_row)
+    return order, _gather_rows_raw(time, order)
+
+
+def temporal_pick_host(sorted_time, start: int, deg: int, bound: int, k: int, replace: bool, strategy: str, seed: int,
+                       stream: int) -> List[int]:
+    """The ranks that the kernels of temporal_neighbor_sample pick for one parent, run on the host:
+    sorted_time is a sequence of integers that holds the row at [start, start + deg), bound the parent's time
+    bound, stream its walk index.  Ranks into the eligible prefix, in slot order."""
+    import ctypes
+
+    times = [int(x) for x in sorted_time]
+    if start < 0 or deg < 0 or start + deg > len(times):
+        raise ValueError("the row leaves sorted_time")
+    arr = (ctypes.c_int64 * max(len(times), 1))(*times)
+    cap = max(deg, int(k), 1)
+    out = (ctypes.c_int64 * cap)()
+    count = int(_lib.load().psa_temporal_pick_host(ctypes.cast(arr, ctypes.c_void_p), int(start), int(deg), int(bound),
+                                                   int(k), int(bool(replace)), TEMPORAL_STRATEGY[strategy],
+                                                   int(seed) & (2**64 - 1), int(stream),
+                                                   ctypes.cast(out, ctypes.c_void_p), cap))
+    if count < 0:
+        raise ValueError("psa_temporal_pick_host refused its arguments")
+    return list(out[:count])
+
+
+def temporal_neighbor_sample(rowptr: torch.Tensor, col: torch.Tensor, order: torch.Tensor, sorted_time: torch.Tensor,
+                             seeds: torch.Tensor, seed_time: torch.Tensor, num_neighbors, strategy: str = "uniform",
+                             replace: bool = False, seed: int = 0, stats: Optional[dict] = None):
+    """Time-bounded per-seed sampling on a square sorted CSR matrix with an EdgeTimeOrder: returns
+    (n_id int64[n], ptr int64[S+1], root int64[S], rowptr' int64[n+1], col' int64[nnz'], e_id int64[nnz']).  Walk
+    list, streams, slot numbering, n_id / ptr / root and the limits are ego_k_hop_sample's, and S * nnz < 2^62 in
+    addition; a parent of ego g picks among the entries of its row with time <= seed_time[g].  The matrix holds
+    the SAMPLED entries, one per distinct (ego, entry), in (ego, entry) order, which is (row', col') order.
+    Host reads (stats["host_reads"]): one per hop with k < 0 that runs, one for n (with the node sort's fault
+    word), one for nnz' (with the edge sort's fault word and the flags; the flags alone when no hop ran); none
+    for S = 0.  Not capturable in a graph: the sizes depend on the data."""
+    rowptr, col, seeds = _index(rowptr, "rowptr"), _index(col, "col"), _index(seeds, "seeds")
+    order, sorted_time = _index(order, "order"), _index(sorted_time, "sorted_time")
+    seed_time = _index(seed_time, "seed_time")
+    if rowptr.numel() < 1:
+        raise ValueError("rowptr must have at least one element")
+    if strategy not in TEMPORAL_STRATEGY:
+        raise ValueError(f"strategy must be 'uniform' or 'last' (got {strategy!r})")
+    if strategy == "last" and replace:
+        raise ValueError("strategy='last' takes the most recent entries: it has no draws to replace")
+    fanouts = [int(k) for k in num_neighbors]
+    if any(k < -1 for k in fanouts):
+        raise ValueError(f"num_neighbors must be >= -1 (got {fanouts})")
+    N, S, nnz, dev = rowptr.numel() - 1, seeds.numel(), col.numel(), rowptr.device
+    if seed_time.numel() != S:
+        raise ValueError(f"seed_time must hold one bound per seed ({S}), got {seed_time.numel()}")
+    if order.numel() != nnz or sorted_time.numel() != nnz:
+        raise ValueError(f"order and sorted_time must hold one element per entry ({nnz})")
+    who = "temporal_neighbor_sample"
+    if S >= 2**31:
+        raise ValueError(f"{who} needs fewer than 2^31 seeds (got {S})")
+    if S * N >= 2**62:
+        raise ValueError(f"{who}: the keys ego * {N} + node of {S} egos do not fit 62 bits")
+    if S * nnz >= 2**62:
+        raise ValueError(f"{who}: the keys ego * {nnz} + entry of {S} egos do not fit 62 bits")
+    bound = key_bound(S, N, who)
+
+    def check_slots(hop, slots, total):
+        if slots >= EGO_MAX_SLOTS:
+            raise ValueError(f"{who}: hop {hop} has {slots} slots, the limit is 2^31 - 16: "
+                             f"to take all eligible entries pass -1, not a large fan-out")
+        if total >= 2**31:
+            raise ValueError(f"{who}: the walk list reaches {total} entries at hop {hop}, the limit is 2^31")
+
+    F, total = S, S
+    for hop, k in enumerate(fanouts, 1):
+        if k <= 0 or F == 0:
+            break
+        F *= k
+        total += F
+        check_slots(hop, F, total)
+    count = {"host_reads": 0, "hops_run": 0, "walk_entries": S}
+    i64 = dict(dtype=torch.int64, device=dev)
+    if S == 0:
+        if stats is not None:
+            stats.update(count)
+        return (torch.empty(0, **i64), torch.zeros(1, **i64), torch.empty(0, **i64), torch.zeros(1, **i64),
+                torch.empty(0, **i64), torch.empty(0, **i64))
+    if N == 0:
+        raise IndexError(f"{who}: a seed lies outside [0, 0)")
+    lib = _lib.load()
+    rep, strat, seed = int(bool(replace)), TEMPORAL_STRATEGY[strategy], int(seed) & (2**64 - 1)
+
+    def raise_on(raised):
+        if raised & EGO_SEED_OUTSIDE:
+            raise IndexError(f"{who}: a seed lies outside [0, {N})")
+        if raised & EGO_COL_OUTSIDE:
+            raise ValueError(f"{who}: a stored column lies outside [0, {N})")
+        if raised & TEMPORAL_BAD_INDEX:
+            raise ValueError(f"{who}: rowptr or the time order do not describe the matrix")
+
+    with _on(dev):
+        flags = torch.empty(1, **i64)
+        node, ego, key = torch.empty(S, **i64), torch.empty(S, dtype=torch.int32, device=dev), torch.empty(S, **i64)
+        check(lib.psa_ego_init(_ptr(seeds), S, N, _ptr(node), _ptr(ego), _ptr(key), S, _ptr(flags), _stream()))
+        keys, ekeys, begin, F, total = [key], [], 0, S, S
+        for hop, k in enumerate(fanouts, 1):
+            if k == 0 or nnz == 0:
+                break
+            pptr = None
+            if k < 0:
+                counts = torch.empty(F, **i64)
+                check(lib.psa_temporal_hop_count(_ptr(rowptr), _ptr(sorted_time), N, nnz, _ptr(seed_time), S,
+                                                 _ptr(node), _ptr(ego), F, _ptr(counts), F, _ptr(flags), _stream()))
+                pptr = count2ptr(counts)
+                slots = int(pptr[-1].item())
+                count["host_reads"] += 1
+                if slots == 0:
+                    break
+            else:
+                slots = F * k
+            total += slots
+            check_slots(hop, slots, total)
+            node2, ego2 = torch.empty(slots, **i64), torch.empty(slots, dtype=torch.int32, device=dev)
+            key2, ekey2 = torch.empty(slots, **i64), torch.empty(slots, **i64)
+            check(lib.psa_temporal_hop_pick(_ptr(rowptr), _ptr(col), _ptr(order), _ptr(sorted_time), N, nnz,
+                                            _ptr(seeds), _ptr(seed_time), S, _ptr(node), _ptr(ego), F, _ptr(pptr),
+                                            begin, k, rep, strat, seed, slots, _ptr(node2), _ptr(ego2), _ptr(key2),
+                                            _ptr(ekey2), slots, _ptr(flags), _stream()))
+            keys.append(key2)
+            ekeys.append(ekey2)
+            begin, F, node, ego = begin + F, slots, node2, ego2
+            count["hops_run"] += 1
+        count["walk_entries"] = total
+        keys = torch.cat(keys) if len(keys) > 1 else keys[0]
+        keys, _, scratch = index_sort(keys, bound, with_sorted_inputs=True, keep_scratch=True)
+        n, _, ego_of, n_id = unique_sorted(keys, N, want_ptr=False, after=scratch)  # the count carries the fault word
+        count["host_reads"] += 1
+        ptr = ind2ptr(ego_of, S)
+        root = torch.empty(S, **i64)
+        if ekeys:
+            # one sentinel of its own, so that the largest distinct key is the sentinel whatever the slots hold
+            ekeys.append(torch.full((1,), S * nnz, **i64))
+            ekeys = torch.cat(ekeys)
+            E = ekeys.numel()
+            ekeys, _, scratch = index_sort(ekeys, S * nnz + 1, with_sorted_inputs=True, keep_scratch=True)
+            ws = _workspace(lib.psa_unique_workspace_bytes(E), dev)
+            count_d, state = torch.empty(2, **i64), torch.empty(3, **i64)
+            check(lib.psa_unique_count_after_sort(_ptr(ekeys), E, _ptr(ws), ws.numel(), _ptr(scratch.ws),
+                                                  scratch.max_value, _ptr(count_d), _stream()))
+            check(lib.psa_temporal_total(_ptr(count_d), _ptr(flags), _ptr(state), _stream()))
+            distinct, fault, raised = state.tolist()  # the one read: nnz' + 1, the sort's fault word, the flags
+        else:
+            distinct, fault, raised = 1, 0, int(flags.item())
+        count["host_reads"] += 1
+        if stats is not None:
+            stats.update(count)
+        if fault:
+            raise HipCoreError("index_sort: an inter-workgroup wait of a radix pass gave up; the order is invalid")
+        raise_on(raised)
+        m = distinct - 1
+        out = torch.empty((3, m), **i64)
+        key_ego = key_edge = None
+        if m > 0:
+            _, _, key_ego, key_edge = unique_sorted(ekeys, nnz, want_ptr=False, _counted=(distinct, ws, count_d))
+        check(lib.psa_temporal_finish(_ptr(rowptr), _ptr(col), N, nnz, _ptr(seeds), S, _ptr(key_ego), _ptr(key_edge), m,
+                                      _ptr(n_id), _ptr(ptr), n, _ptr(root), S, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                                      m, _ptr(flags), _stream()))
+        rowptr_out = ind2ptr(out[0], n) if m > 0 else torch.zeros(n + 1, **i64)
+    return n_id, ptr, root, rowptr_out, out[1], out[2]
+
+
 # ---- reverse_cuthill_mckee (csrc/rcm.hip) ---------------------------------------------------------
 
 RCM_DONE, RCM_HANDOVER, RCM_BAD_INPUT = 0, 1, 2
