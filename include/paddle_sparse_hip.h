@@ -1621,6 +1621,47 @@ int64_t psa_temporal_pick_host(const int64_t* sorted_time, int64_t start, int64_
                                int replace, int strategy, uint64_t seed, int64_t stream_index, int64_t* ranks,
                                int64_t ranks_count);
 
+/* ---- segment_topk: keep the k greatest entries of every segment (csrc/topk.hip,
+ * csrc/topk_select.h).  A selection by value, not a sort: nothing is reordered.
+ *
+ * Segment s holds the positions j in [indptr[s], indptr[s + 1]); its element is
+ * x_j = value[perm ? perm[j] : j].  value is `dtype`[n] (PSA_F32, PSA_F64, PSA_I32, PSA_I64,
+ * PSA_F16 or PSA_BF16), indptr int64[nseg + 1]; perm (int64[n], may be NULL) is trusted to be a
+ * permutation of [0, n): with the csr2csc of a CSR matrix and its colptr the segments are the
+ * columns, and nothing is transposed.
+ *
+ * Key.  Every element maps to an unsigned key of 32 bits (fp32, fp16, bf16, int32) or 64 bits
+ * (fp64, int64) that preserves the value order.  Every NaN, whatever its sign or payload, maps
+ * to the single greatest key (torch.topk's rule for both directions); -0.0 and +0.0 map to one
+ * key; with largest == 0 the key is complemented, so the rule below only ever keeps the k
+ * greatest keys (NaN is then the least wanted).
+ *
+ * Rule.  Entry j of segment s is kept iff
+ *   #{j' in s : key(j') > key(j)} + #{j' in s : key(j') == key(j), j' < j} < k_s,
+ * so exactly min(max(k_s, 0), len_s) entries are kept and ties go to the earlier position in
+ * segment order.  k_s = k_seg[s] when k_seg (int64[nseg]) is given, the scalar k otherwise;
+ * k_s <= 0 keeps nothing.  The result is a pure function of the input and repeats bit for bit.
+ *
+ * Output.  keep[perm ? perm[j] : j] = 1 or 0 (uint8[n], in storage order).  Every position
+ * inside a valid segment is written and nothing else is.  A segment whose bounds do not satisfy
+ * 0 <= begin <= end <= n reads nothing and writes nothing.
+ *
+ * Two launches at most, no workspace, no host read, capturable: groups of 8 .. 64 lanes rank
+ * the segments of up to 64 entries in registers; workgroups find the threshold of the longer
+ * ones by an MSB-first radix select with 8-bit digits, their keys in LDS up to 4096 entries and
+ * read again from global memory by every pass above.
+ *
+ * PSA_ERR_INVALID_ARG: a negative size, an unknown dtype, more than 2^31 - 1 workgroups, or,
+ * with n > 0 and nseg > 0, a NULL value, indptr or keep.  nseg == 0 or n == 0 returns PSA_OK
+ * and touches nothing.
+ *
+ * psa_segment_topk_host runs the same steps (key mapping, digit passes, ordered write)
+ * serially on HOST arrays: every result can be checked without a GPU. */
+int psa_segment_topk(const void* value, int dtype, const int64_t* perm, const int64_t* indptr, int64_t nseg, int64_t n,
+                     int64_t k, const int64_t* k_seg, int largest, uint8_t* keep, psa_stream_t stream);
+int psa_segment_topk_host(const void* value, int dtype, const int64_t* perm, const int64_t* indptr, int64_t nseg,
+                          int64_t n, int64_t k, const int64_t* k_seg, int largest, uint8_t* keep);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

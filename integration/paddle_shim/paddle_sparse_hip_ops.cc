@@ -1182,3 +1182,35 @@ PD_BUILD_OP(sddmm_heads)
     .Inputs({"rowptr", "col", "x", "y"})
     .Outputs({"out"})
     .SetKernelFn(PD_KERNEL(sddmm_heads));
+
+// segment_topk: keep uint8[n], 1 for the k greatest (largest = false: smallest) of value[perm[j]] over the positions j
+// of every segment of ptr, 0 for the others, in value's order (the rule, NaN and the tie order: the header).  k_seg
+// (int64, one per segment) overrides the scalar k.  One call, no scratch, no host read; the seam (topk.py of the port)
+// takes the kept positions with nonzero() and gathers row, col and value there.
+std::vector<paddle::Tensor> segment_topk(paddle::Tensor& value, paddle::Tensor& ptr,
+                                         const paddle::optional<paddle::Tensor>& perm,
+                                         const paddle::optional<paddle::Tensor>& k_seg, int64_t k, bool largest) {
+  CHECK_GPU(value);
+  CHECK_GPU(ptr);
+  CHECK_I64(ptr);
+  PD_CHECK(value.shape().size() == 1, "segment_topk selects by a 1-D key");
+  PD_CHECK(ptr.numel() >= 1, "ptr must have at least one element");
+  const int64_t n = value.numel(), nseg = ptr.numel() - 1;
+  if (perm) {
+    CHECK_I64(perm.get());
+    PD_CHECK(perm.get().numel() == n, "perm must have one entry per value");
+  }
+  if (k_seg) {
+    CHECK_I64(k_seg.get());
+    PD_CHECK(k_seg.get().numel() == nseg, "k_seg must have one entry per segment");
+  }
+  auto keep = paddle::full({n}, 0, paddle::DataType::UINT8, value.place());
+  PSA_CALL(psa_segment_topk(value.data(), dtype_id_of(value), i64_or_null(perm), i64(ptr), nseg, n, k, i64_or_null(k_seg),
+                            largest ? 1 : 0, keep.data<uint8_t>(), stream_of(value)));
+  return {keep};
+}
+PD_BUILD_OP(segment_topk)
+    .Inputs({"value", "ptr", paddle::Optional("perm"), paddle::Optional("k_seg")})
+    .Outputs({"keep"})
+    .Attrs({"k: int64_t", "largest: bool"})
+    .SetKernelFn(PD_KERNEL(segment_topk));

@@ -75,6 +75,7 @@ if not _running_the_builder():
         ("masked", ("masked_spspmm", "common_neighbors", "triangle_count")),
         ("negative", ("edge_ids", "has_edge", "negative_sampling", "structured_negative_sampling")),
         ("components", ("connected_components", "largest_connected_components")),
+        ("topk", ("topk", "segment_topk")),
     )
 
     __all__ = ["__version__"]

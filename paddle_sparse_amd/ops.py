@@ -3257,3 +3257,101 @@ def pair_intersect(x, y, pair_x: torch.Tensor, pair_y: torch.Tensor, weight: Opt
                                              _ptr(y_ptr), _ptr(y_idx), _ptr(y_val), y_ptr.numel() - 1, _ptr(weight),
                                              _ptr(pair_x), _ptr(pair_y), P, _ptr(out), _stream()))
     return out
+
+
+# ---- segmented top-k selection (csrc/topk.hip) -------------------------------------------
+
+TOPK_SHORT, TOPK_LDS = 64, 4096  # segment lengths up to which the keys sit in registers / in LDS
+TOPK_GRID, TOPK_CHUNK = 2048, 256  # workgroups of the long-segment kernel; segments each takes per trip
+
+
+def _topk_k(k, nseg: int):
+    """(scalar k, k_seg or None) from an int or an int64[nseg] array / tensor."""
+    if isinstance(k, bool):
+        raise TypeError("k must be an int or an int64 tensor with one entry per segment")
+    if isinstance(k, int):
+        return k, None
+    if not hasattr(k, "dtype") or "int64" not in str(k.dtype):
+        raise TypeError("k must be an int or an int64 tensor with one entry per segment")
+    if k.ndim != 1 or k.shape[0] != nseg:
+        raise ValueError(f"k must have one entry per segment ({nseg}), got shape {tuple(k.shape)}")
+    return 0, k
+
+
+def segment_topk(value: torch.Tensor, indptr: torch.Tensor, k, perm: Optional[torch.Tensor] = None,
+                 largest: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """keep uint8[n]: 1 for the k greatest (largest=False: smallest) of value[perm[j]] over the positions j
+    of every segment of indptr (int64[nseg + 1]), 0 for the others, in value's order.  value is 1-D
+    float32, float64, int32, int64, float16 or bfloat16; k an int or an int64[nseg] tensor (k <= 0 keeps
+    nothing, k >= the length everything).  NaN counts as the greatest value in both directions, -0.0
+    equals +0.0, ties go to the earlier position of the segment (include/paddle_sparse_hip.h states the
+    rule in full).  keep starts zero-filled unless out (uint8[n]) is given: only positions inside a valid
+    segment are written.  One or two launches, no scratch, no host read: capturable.  Not differentiable."""
+    _gpu(value, "value")
+    if value.dtype not in _DTYPE_ID:
+        raise TypeError(f"segment_topk: unsupported value dtype {value.dtype}")
+    if value.dim() != 1:
+        raise ValueError(f"segment_topk: value must be 1-D (got {tuple(value.shape)})")
+    value, indptr = value.detach().contiguous(), _index(indptr, "indptr")
+    n, nseg, dev = value.numel(), indptr.numel() - 1, value.device
+    if nseg < 0:
+        raise ValueError("indptr must not be empty")
+    k, k_seg = _topk_k(k, nseg)
+    if k_seg is not None:
+        k_seg = _index(k_seg, "k")
+    if perm is not None:
+        perm = _index(perm, "perm")
+        if perm.numel() != n:
+            raise ValueError(f"perm must have one entry per value ({n}), got {perm.numel()}")
+    for name, t in (("indptr", indptr), ("k", k_seg), ("perm", perm)):
+        if t is not None and t.device != dev:
+            raise ValueError(f"segment_topk: {name} is on {t.device}, value on {dev}")
+    if out is None:
+        out = torch.zeros(n, dtype=torch.uint8, device=dev)
+    else:
+        _gpu(out, "out")
+        if out.dtype != torch.uint8 or out.dim() != 1 or out.numel() != n or not out.is_contiguous() \
+                or out.device != dev:
+            raise ValueError(f"out must be a contiguous uint8[{n}] tensor on {dev}")
+    if n > 0 and nseg > 0:
+        with _on(dev):
+            check(_lib.load().psa_segment_topk(_ptr(value), _DTYPE_ID[value.dtype], _ptr(perm), _ptr(indptr), nseg, n,
+                                               int(k), _ptr(k_seg), int(bool(largest)), _ptr(out), _stream()))
+    return out
+
+
+_TOPK_HOST_DTYPES = {"float32": 0, "float64": 1, "int32": 2, "int64": 3, "float16": 4}
+
+
+def segment_topk_host(value, indptr, k, perm=None, largest: bool = True, out=None, dtype: Optional[str] = None):
+    """segment_topk run serially on the host by the kernels' own steps (numpy arrays in, keep uint8[n]
+    numpy out): what the CPU suite holds the restatement to.  dtype="bfloat16" reads a uint16 array as
+    bfloat16 bits (numpy has no such type)."""
+    import numpy as np
+
+    value = np.ascontiguousarray(value)
+    if dtype == "bfloat16":
+        if value.dtype != np.uint16:
+            raise TypeError("dtype='bfloat16' takes the bits as a uint16 array")
+        dtype_id = 5
+    elif dtype is None and value.dtype.name in _TOPK_HOST_DTYPES:
+        dtype_id = _TOPK_HOST_DTYPES[value.dtype.name]
+    else:
+        raise TypeError(f"segment_topk_host: unsupported value dtype {value.dtype} (dtype={dtype!r})")
+    indptr = np.ascontiguousarray(indptr, np.int64)
+    if value.ndim != 1 or indptr.ndim != 1 or indptr.size < 1:
+        raise ValueError("value must be 1-D, indptr 1-D and not empty")
+    n, nseg = value.size, indptr.size - 1
+    k, k_seg = _topk_k(k, nseg)
+    k_seg = None if k_seg is None else np.ascontiguousarray(k_seg, np.int64)
+    perm = None if perm is None else np.ascontiguousarray(perm, np.int64)
+    if perm is not None and perm.shape != (n,):
+        raise ValueError(f"perm must have one entry per value ({n})")
+    if out is None:
+        out = np.zeros(n, np.uint8)
+    elif out.dtype != np.uint8 or out.shape != (n,) or not out.flags.c_contiguous:
+        raise ValueError(f"out must be a contiguous uint8[{n}] array")
+    ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    check(_lib.load().psa_segment_topk_host(ptr(value), dtype_id, ptr(perm), ptr(indptr), nseg, n, int(k), ptr(k_seg),
+                                            int(bool(largest)), ptr(out)))
+    return out
