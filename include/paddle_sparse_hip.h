@@ -1662,6 +1662,66 @@ int psa_segment_topk(const void* value, int dtype, const int64_t* perm, const in
 int psa_segment_topk_host(const void* value, int dtype, const int64_t* perm, const int64_t* indptr, int64_t nseg,
                           int64_t n, int64_t k, const int64_t* k_seg, int largest, uint8_t* keep);
 
+/* ---- ppr: approximate personalised PageRank of an N x N CSR pattern by forward push, in
+ * fixed point (csrc/ppr.hip, csrc/ppr_step.h).  Only the pattern is read; a duplicated entry
+ * counts twice; deg(u) = rowptr[u + 1] - rowptr[u].
+ *
+ * Units.  ONE = 2^48 is the mass of a source, alpha = alpha_q / 2^32, eps = eps_q / 2^48.
+ * For source s the state is r (residual) and p (score), unsigned integers per node, r[s] = ONE
+ * at the start.  A round: u is active iff r[u] >= eps_q * max(deg(u), 1) on the state at the
+ * start of the round; every active u with x = r[u] is split,
+ *   deg(u) == 0:  p[u] += x, r[u] = 0
+ *   otherwise:    keep = (x * alpha_q) >> 32, share = (x - keep) / deg(u) (floored),
+ *                 p[u] += keep, r[u] = x - keep - share * deg(u),
+ * and after all splits r[v] += share(u) for every stored column v of every split u.  Rounds
+ * repeat until one has no active node or max_rounds have run.  sum(p) + sum(r) == ONE always.
+ * With k0 = (alpha_q * eps_q) >> 32 the degrees of all pushes of a run add up to at most
+ * bound = ONE / k0 (integer division), at most 1 + bound nodes are touched and at most
+ * bound + 1 rounds run.  Integer adds commute: p and r are the same bits on every run.
+ *
+ * Tables.  Source i of the call owns slab i of four caller-provided arrays, table_key
+ * (int64[nsrc * cap]) and table_r, table_p, table_s (uint64[nsrc * cap] each): an
+ * open-addressing table of cap slots, cap a power of two, linear probing from a hash of the
+ * node, at most cap probes.  After the call slot j of slab i holds key -1 (free; its p is not
+ * meaningful when the table ran in global memory) or a node with its r and p; which slot a
+ * node has is not defined.  table_s is the kernel's scratch (the share a split leaves for
+ * the entry phase).  The slabs need no initialisation.  cap >= 2 * min(N, 1 + bound) always
+ * suffices.  When no slot is found the add is dropped and PSA_PPR_TABLE_FULL is raised for
+ * that source; a column or row bound outside the matrix or a source outside [0, N) raises
+ * PSA_PPR_BAD_INDEX and is skipped.  No address outside the slabs is formed in either case.
+ *
+ * info is int64[8 * nsrc], field k of source i at info[k * nsrc + i]: 0 nodes with p > 0,
+ * 1 nodes with r > 0, 2 rounds that had an active node, 3 flags (PSA_PPR_*), 4 pushes,
+ * 5 sum of deg over the pushes (= integer atomics issued), 6 slots in use, 7 zero.
+ *
+ * One workgroup per source, one launch.  Tables of cap <= psa_ppr_lds_cap() (4096) live in
+ * LDS for the whole run (PSA_PPR_IN_LDS is set) and are copied to the slab at the end.
+ *
+ * psa_ppr_write compacts slabs into keys and values for the caller's sort: for slab i, every
+ * slot with a key in [0, N) and table_val != 0 gives, at some position in [ptr[i], ptr[i + 1]),
+ * key_out = i * N + node and val_out = table_val / 2^48 (exact in a double).  table_val is
+ * table_p or table_r; ptr is int64[nslab + 1], e.g. count2ptr of info's field 0 or 1.  A slab
+ * whose range is not inside [0, n_out] writes nothing.
+ *
+ * PSA_ERR_INVALID_ARG: a negative size, a cap that is no power of two, alpha_q outside
+ * [2^16, 2^32 - 2^16], eps_q outside [2^16, 2^48], more than 2^31 - 1 sources, or a NULL that
+ * the call would read (col may be NULL when nnz == 0).  nsrc == 0 (nslab == 0, n_out == 0)
+ * returns PSA_OK and touches nothing.
+ *
+ * psa_ppr_host runs the same steps serially on HOST arrays. */
+#define PSA_PPR_TABLE_FULL 1
+#define PSA_PPR_BAD_INDEX 2
+#define PSA_PPR_IN_LDS 4
+int64_t psa_ppr_lds_cap(void);
+int psa_ppr_push(const int64_t* rowptr, const int64_t* col, int64_t N, int64_t nnz, const int64_t* source, int64_t nsrc,
+                 int64_t cap, uint64_t alpha_q, uint64_t eps_q, int64_t max_rounds, int64_t* table_key,
+                 uint64_t* table_r, uint64_t* table_p, uint64_t* table_s, int64_t* info, psa_stream_t stream);
+int psa_ppr_write(const int64_t* table_key, const uint64_t* table_val, int64_t nslab, int64_t cap, int64_t N,
+                  const int64_t* ptr, int64_t n_out, int64_t* key_out, double* val_out, psa_stream_t stream);
+int psa_ppr_host(const int64_t* rowptr, const int64_t* col, int64_t N, int64_t nnz, const int64_t* source, int64_t nsrc,
+                 int64_t cap, uint64_t alpha_q, uint64_t eps_q, int64_t max_rounds, int64_t* table_key,
+                 uint64_t* table_r, uint64_t* table_p, uint64_t* table_s, int64_t* info);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -76,6 +76,7 @@ if not _running_the_builder():
         ("negative", ("edge_ids", "has_edge", "negative_sampling", "structured_negative_sampling")),
         ("components", ("connected_components", "largest_connected_components")),
         ("topk", ("topk", "segment_topk")),
+        ("ppr", ("ppr",)),
     )
 
     __all__ = ["__version__"]

@@ -3355,3 +3355,80 @@ def segment_topk_host(value, indptr, k, perm=None, largest: bool = True, out=Non
     check(_lib.load().psa_segment_topk_host(ptr(value), dtype_id, ptr(perm), ptr(indptr), nseg, n, int(k), ptr(k_seg),
                                             int(bool(largest)), ptr(out)))
     return out
+
+
+# ---- personalised PageRank by forward push (csrc/ppr.hip) ---------------------------------
+
+PPR_ONE = 1 << 48  # the fixed-point unit of r and p
+PPR_TABLE_FULL, PPR_BAD_INDEX, PPR_IN_LDS = 1, 2, 4  # bits of info's flags field
+PPR_INFO = ("count_p", "count_r", "rounds", "flags", "pushes", "edges", "touched")  # info's fields, in order
+
+
+def ppr_lds_cap() -> int:
+    """The largest table (slots) that psa_ppr_push keeps in LDS."""
+    return _lib.load().psa_ppr_lds_cap()
+
+
+def ppr_tables(nslab: int, cap: int, device) -> Tuple[torch.Tensor, ...]:
+    """(key, r, p, s): the four int64[nslab * cap] arrays of ppr_push (r, p and s hold uint64 bits
+    below 2^63).  They need no initialisation and may be used again by the next batch."""
+    return tuple(torch.empty(nslab * cap, dtype=torch.int64, device=device) for _ in range(4))
+
+
+def ppr_push(rowptr: torch.Tensor, col: torch.Tensor, N: int, source: torch.Tensor, cap: int, alpha_q: int, eps_q: int,
+             max_rounds: int, tables: Optional[Tuple[torch.Tensor, ...]] = None):
+    """Runs the forward push of every source (int64[S]) to its end or for max_rounds rounds, one
+    workgroup per source, in slab i of `tables` (ppr_tables(S, cap); made here when None).  Returns
+    (tables, info) with info int64[8, S] on the device, rows as PPR_INFO.  One launch, no host read;
+    the header states the rule, the table and the flags."""
+    rowptr, col, source = _index(rowptr, "rowptr"), _index(col, "col"), _index(source, "source")
+    S, dev = source.numel(), rowptr.device
+    if rowptr.numel() != N + 1:
+        raise ValueError(f"rowptr must have N + 1 = {N + 1} elements (got {rowptr.numel()})")
+    if tables is None:
+        tables = ppr_tables(S, cap, dev)
+    for t in tables:
+        if t.dtype != torch.int64 or t.dim() != 1 or t.numel() < S * cap or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"every table must be a contiguous int64 tensor of at least S * cap = {S * cap} elements on {dev}")
+    info = torch.empty((8, S), dtype=torch.int64, device=dev)
+    with _on(dev):
+        check(_lib.load().psa_ppr_push(_ptr(rowptr), _ptr(col), N, col.numel(), _ptr(source), S, cap, alpha_q, eps_q,
+                                       max_rounds, *(_ptr(t) for t in tables), _ptr(info), _stream()))
+    return tables, info
+
+
+def ppr_write(table_key: torch.Tensor, table_val: torch.Tensor, nslab: int, cap: int, N: int, ptr: torch.Tensor,
+              n_out: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(key int64[n_out], value float64[n_out]): for slab i the nodes whose table_val (the r or the p
+    array of ppr_push) is not zero, as key = i * N + node and value = table_val / 2^48, in no particular
+    order inside [ptr[i], ptr[i + 1]).  ptr is int64[nslab + 1], n_out its last element.  One launch."""
+    ptr = _index(ptr, "ptr")
+    if ptr.numel() != nslab + 1:
+        raise ValueError(f"ptr must have nslab + 1 = {nslab + 1} elements")
+    if min(table_key.numel(), table_val.numel()) < nslab * cap:
+        raise ValueError("the tables are shorter than nslab * cap")
+    dev = ptr.device
+    key = torch.empty(n_out, dtype=torch.int64, device=dev)
+    val = torch.empty(n_out, dtype=torch.float64, device=dev)
+    with _on(dev):
+        check(_lib.load().psa_ppr_write(_ptr(_index(table_key, "table_key")), _ptr(_index(table_val, "table_val")),
+                                        nslab, cap, N, _ptr(ptr), n_out, _ptr(key), _ptr(val), _stream()))
+    return key, val
+
+
+def ppr_host(rowptr, col, N: int, source, cap: int, alpha_q: int, eps_q: int, max_rounds: int):
+    """ppr_push run serially on the host by the kernel's own steps (numpy arrays in; key int64[S, cap],
+    r and p uint64[S, cap], info int64[8, S] out): what the CPU suite holds the restatement to."""
+    import numpy as np
+
+    rowptr, col, source = (np.ascontiguousarray(a, np.int64) for a in (rowptr, col, source))
+    if rowptr.shape != (N + 1,) or col.ndim != 1 or source.ndim != 1:
+        raise ValueError("rowptr must be int64[N + 1], col and source 1-D")
+    S = source.size
+    key = np.full((S, cap), -7, np.int64)
+    r, p, s = (np.full((S, cap), 7, np.uint64) for _ in range(3))
+    info = np.full((8, S), -7, np.int64)
+    check(_lib.load().psa_ppr_host(rowptr.ctypes.data, col.ctypes.data, N, col.size, source.ctypes.data, S, cap, alpha_q,
+                                   eps_q, max_rounds, key.ctypes.data, r.ctypes.data, p.ctypes.data, s.ctypes.data,
+                                   info.ctypes.data))
+    return key, r, p, info
