@@ -1,4 +1,4 @@
-// Shared host-side helpers for the C-ABI core (gfx950 only).
+// Shared helpers for the C-ABI core (gfx950 only): errors, workspaces, grids, the flag word.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -21,6 +21,25 @@ inline hipStream_t as_stream(psa_stream_t s) {
 constexpr int kWave = 64;  // gfx950 wavefront
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Workgroups of `per` items that cover n items (one for none); per defaults to the 256 threads
+// of a one-item-per-lane launch.  For counts that the entry point has bounded already.
+inline unsigned blocks_for(int64_t n, int per = 256) {
+  return static_cast<unsigned>(ceil_div(n > 0 ? n : 1, per));
+}
+
+// The same for a count nothing bounds: false when the grid would not fit one launch.
+inline bool grid_for(int64_t n, unsigned* blocks) {
+  const int64_t b = ceil_div(n > 0 ? n : 1, 256);
+  if (b > 0x7fffffff) return false;
+  *blocks = static_cast<unsigned>(b);
+  return true;
+}
+
+// Bits of a flag word that many lanes raise and the host reads once.
+__device__ __forceinline__ void raise_flag(int64_t* word, unsigned long long bits) {
+  atomicOr(reinterpret_cast<unsigned long long*>(word), bits);
+}
 
 inline bool aligned(const void* p, size_t a) {
   return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0;

@@ -6,8 +6,8 @@
 // per row with no atomics: a binary search of the row's sorted columns gives
 // the first diagonal entry and their number (duplicates included).  The write
 // pass is balanced by OUTPUT entries: a workgroup owns a fixed tile of the
-// output, finds the rows the tile spans by a 64-ary wave search in the new
-// rowptr, stages those rows' pointers in LDS (as ptr2ind_kernel does in
+// output, finds the rows the tile spans by a 64-ary wave search (search.h) in the
+// new rowptr, stages those rows' pointers in LDS (as ptr2ind_kernel does in
 // convert.hip) and maps every output slot to its source entry or to the
 // inserted diagonal value.  A hub row is split over as many tiles as it
 // needs; no lane walks more than kPer entries.  Values move as opaque rows of
@@ -16,6 +16,7 @@
 #include <initializer_list>
 
 #include "common.h"
+#include "search.h"
 
 namespace {
 
@@ -51,21 +52,7 @@ __device__ __forceinline__ bool on_diag(int64_t r, int64_t M, int64_t N, int64_t
   return r >= 0 && r < M && c >= 0 && c < N;
 }
 
-// Largest r in [lo, hi) with ptr[r] <= p, given ptr[lo] <= p; called by a whole
-// wave (64 probes per step: 4 dependent loads for 2^24 rows).
-__device__ __forceinline__ int64_t wave_search(const int64_t* __restrict__ ptr, int64_t lo, int64_t hi, int64_t p) {
-  const int lane = threadIdx.x & 63;
-  while (hi - lo > 1) {
-    const int64_t step = (hi - lo + 63) / 64;
-    const int64_t x = lo + lane * step;
-    const bool ok = x < hi && ptr[x] <= p;
-    const int cnt = __popcll(__ballot(ok));  // lanes [0, cnt) hold: ptr is non-decreasing
-    const int64_t nhi = lo + cnt * step;
-    lo += (cnt - 1) * step;
-    hi = nhi < hi ? nhi : hi;
-  }
-  return lo;
-}
+using psa::wave_search;
 
 // One lane per j in [0, max(M, N)): row j's diagonal entries [dpos[j], dpos[j] + cnt)
 // and its new length; with colcount given, column j's count adjusted for row j - k

@@ -6,7 +6,7 @@
 // Walk list: one global sequence of entries, entry i < S is seed i and belongs to ego i.
 // Hop l expands EVERY entry of hop l - 1, duplicates included; a child belongs to its
 // parent's ego.  The parent at walk index i holding node v makes sample_adj's picks for
-// (deg(v), k, replace) on stream i of `seed`.  k >= 0: the hop has F * k slots, slot
+// (deg(v), k, replace) on stream i of `seed` (uniform_pick.h; the searches are search.h's).  k >= 0: the hop has F * k slots, slot
 // f * k + t is pick t of parent f, a slot past its parent's picks (or of an empty parent) is
 // empty: node -1, and it stays empty in later hops.  k < 0: the slots are the entries of the
 // parents' rows in (parent, storage) order, all valid.
@@ -43,7 +43,8 @@
 #include <atomic>
 
 #include "common.h"
-#include "rng.h"
+#include "search.h"
+#include "uniform_pick.h"
 
 namespace {
 
@@ -51,33 +52,17 @@ constexpr int kThreads = 256;
 constexpr int kWavesPerBlock = kThreads / psa::kWave;
 constexpr int kGroup = 8;
 constexpr int kRowsPerWave = psa::kWave / kGroup;
-constexpr int kFloydRegs = 32;
-constexpr int64_t kMaxSlots = 0x7ffffff0;
 constexpr int64_t kMaxBlocks = 65536;
 constexpr unsigned long long kSeedOutside = PSA_EGO_SEED_OUTSIDE, kColOutside = PSA_EGO_COL_OUTSIDE;
 
 std::atomic<int> g_threshold{32};  // probe sides LONGER than this take the whole wave
 
-__device__ __forceinline__ void raise_flag(int64_t* flags, unsigned long long bit) {
-  atomicOr(reinterpret_cast<unsigned long long*>(flags), bit);
-}
-
-__device__ __forceinline__ int64_t picks_of(int64_t deg, int64_t k, int replace) {
-  if (replace) return deg > 0 ? k : 0;
-  return deg < k ? deg : k;
-}
-
-// start and degree of the row of node v; an empty entry (-1) has no entries
-__device__ __forceinline__ void row_of(const int64_t* __restrict__ rowptr, int64_t N, int64_t v, int64_t* start,
-                                       int64_t* deg) {
-  if (static_cast<uint64_t>(v) >= static_cast<uint64_t>(N)) {
-    *start = 0;
-    *deg = 0;
-    return;
-  }
-  *start = rowptr[v];
-  *deg = rowptr[v + 1] - *start;
-}
+using psa::blocks_for;
+using psa::kFloydRegs;
+using psa::kMaxSlots;
+using psa::picks_of;
+using psa::raise_flag;
+using psa::row_of;  // an empty entry (-1) has no entries
 
 // the node that stands in for an empty slot of ego g: its seed (0 for a seed outside: the flag is up)
 __device__ __forceinline__ int64_t seed_of(const int64_t* __restrict__ seeds, int64_t N, int64_t g) {
@@ -135,8 +120,8 @@ ego_pick_slot_kernel(const int64_t* __restrict__ rowptr, const int64_t* __restri
   emit(col, seeds, N, e, g, p, node_out, key_out, flags);
 }
 
-// Without replacement, deg > k: Floyd's walk as sample_adj does it, one thread per parent,
-// the picks in registers.
+// Without replacement, deg > k: Floyd's walk as sample_adj does it (uniform_pick.h, the draw
+// in [0, j)), one thread per parent, the picks in registers.
 template <int KMAX>
 __global__ void __launch_bounds__(kThreads)
 ego_pick_floyd_reg_kernel(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col, int64_t N,
@@ -150,18 +135,7 @@ ego_pick_floyd_reg_kernel(const int64_t* __restrict__ rowptr, const int64_t* __r
   row_of(rowptr, N, pnode[f], &start, &deg);
   if (deg <= k) return;
   int64_t mine[KMAX];
-  const uint64_t stream = psa::rand_stream(seed, begin + f);
-#pragma unroll
-  for (int t = 0; t < KMAX; ++t) {
-    if (t < k) {
-      const int64_t j = deg - k + t;  // > 0
-      const int64_t pick = start + psa::rand_draw(stream, t, j);
-      bool taken = false;
-#pragma unroll
-      for (int u = 0; u < t; ++u) taken |= mine[u] == pick;
-      mine[t] = taken ? start + j : pick;
-    }
-  }
+  psa::floyd_walk_regs<KMAX, psa::kDrawHalfOpen>(deg, k, psa::rand_stream(seed, begin + f), start, mine);
   const int32_t g = pego[f];
 #pragma unroll
   for (int t = 0; t < KMAX; ++t)
@@ -180,15 +154,7 @@ ego_pick_floyd_kernel(const int64_t* __restrict__ rowptr, const int64_t* __restr
   row_of(rowptr, N, pnode[f], &start, &deg);
   if (deg <= k) return;
   int64_t* mine = node_out + f * k;
-  const uint64_t stream = psa::rand_stream(seed, begin + f);
-  for (int64_t t = 0; t < k; ++t) {
-    const int64_t j = deg - k + t;  // > 0
-    int64_t pick = start + psa::rand_draw(stream, t, j);
-    bool taken = false;
-    for (int64_t u = 0; u < t && !taken; ++u) taken = mine[u] == pick;
-    if (taken) pick = start + j;
-    mine[t] = pick;
-  }
+  psa::floyd_walk<psa::kDrawHalfOpen>(deg, k, psa::rand_stream(seed, begin + f), start, mine);
   // entries become nodes after the walk, whose comparisons must see entries only
   const int32_t g = pego[f];
   for (int64_t t = 0; t < k; ++t) emit(col, seeds, N, mine[t], g, f * k + t, node_out, key_out, flags);
@@ -203,12 +169,7 @@ ego_pick_all_kernel(const int64_t* __restrict__ rowptr, const int64_t* __restric
                     int64_t* __restrict__ flags) {
   const int64_t p = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
   if (p >= cap) return;
-  int64_t lo = 0, hi = F;  // pptr[0] = 0 <= p < cap = pptr[F]
-  while (hi - lo > 1) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (pptr[mid] <= p) lo = mid;
-    else hi = mid;
-  }
+  const int64_t lo = psa::last_le(pptr, 0, F, p);  // pptr[0] = 0 <= p < cap = pptr[F]
   const int32_t g = pego[lo];
   ego_out[p] = g;
   int64_t start, deg;
@@ -232,14 +193,7 @@ ego_root_kernel(const int64_t* __restrict__ n_id, const int64_t* __restrict__ pt
                 int64_t S, int64_t* __restrict__ root) {
   const int64_t g = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
   if (g >= S) return;
-  const int64_t s = seeds[g], end = ptr[g + 1];
-  int64_t lo = ptr[g], hi = end;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (n_id[mid] < s) lo = mid + 1;
-    else hi = mid;
-  }
-  root[g] = lo < end && n_id[lo] == s ? lo : -1;
+  root[g] = psa::first_equal(n_id, ptr[g], ptr[g + 1], seeds[g]);
 }
 
 __global__ void ego_total_kernel(const int64_t* __restrict__ rowptr_out, int64_t n, const int64_t* __restrict__ flags,
@@ -398,10 +352,6 @@ ego_induce_kernel(const int64_t* __restrict__ rowptr, const int64_t* __restrict_
       }
     }
   }
-}
-
-unsigned blocks_for(int64_t n, int per = kThreads) {
-  return static_cast<unsigned>(psa::ceil_div(n > 0 ? n : 1, per));
 }
 
 unsigned induce_blocks(int64_t n) {

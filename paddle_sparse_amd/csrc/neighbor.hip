@@ -6,7 +6,7 @@
 // n_id starts as the seeds; local id = position in n_id.  Hop l expands the nodes that
 // hop l - 1 appended (the frontier, local ids [begin, end)), each node once per call.  A
 // frontier node at local id i makes picks_of(deg, k_l, replace) picks by sample_adj's
-// rules with the draws of rng.h on stream i, so one seed serves every hop.  Slot order
+// rules (uniform_pick.h) with the draws of rng.h on stream i, so one seed serves every hop.  Slot order
 // within a hop is (frontier position, t); a picked column without a local id gets the
 // next one in order of its first slot.
 //
@@ -19,7 +19,7 @@
 //               reads the slot count
 //   hop_pick    one thread per slot p picks its entry e_raw[p] (k >= 0: p = f * k + t, the
 //               grid covers the bound F * k and slots past a row's picks stay -1; k < 0:
-//               a tile of kTile slots finds its rows by a wave search in the scanned
+//               a tile of kTile slots finds its rows by search.h's wave search in the scanned
 //               degrees and stages them in LDS, so a hub row spreads over many
 //               workgroups), Floyd rows one thread per row (picks in registers up to
 //               k = 32); every slot does one atomicMax(local[c], -2 - p): ids are >= 0
@@ -34,7 +34,8 @@
 //   reset       local[n_id[j]] = kUnseen for the touched entries: n stores instead of N
 // No workgroup waits for another one; every loop is bounded by a degree, k or log2(F).
 #include "common.h"
-#include "rng.h"
+#include "search.h"
+#include "uniform_pick.h"
 #include "weighted_pick.h"
 
 namespace {
@@ -43,43 +44,25 @@ constexpr int kThreads = 256;
 constexpr int kPer = 4;                  // slots per lane per tile (k < 0)
 constexpr int kTile = kThreads * kPer;   // slots per workgroup (k < 0)
 constexpr int kRows = 512;               // rows of a tile staged in LDS
-constexpr int kFloydRegs = 32;           // largest fan-out whose Floyd picks stay in registers
-constexpr int32_t kUnseen = INT32_MIN;
-constexpr int64_t kMaxSlots = 0x7ffffff0;  // -2 - p must stay above kUnseen
+constexpr int32_t kUnseen = INT32_MIN;   // psa::kMaxSlots keeps -2 - p above it
 
 // the caller's state block, int64[PSA_NEIGHBOR_STATE_WORDS]
 enum { kEdges = 0, kNew, kFlags, kWords };
 static_assert(kWords <= PSA_NEIGHBOR_STATE_WORDS, "state block");
 constexpr unsigned long long kDupSeed = 1, kSeedOutside = 2, kColOutside = 4;
 
+using psa::blocks_for;
+using psa::kFloydRegs;
+using psa::kMaxSlots;
+using psa::picks_of;
+using psa::raise_flag;
 using psa::randint;
+using psa::row_of;  // a frontier node outside the matrix is a bad seed: the flag is up and the call will raise
+using psa::wave_search;
 
 __device__ __forceinline__ int32_t ld32(const int32_t* p) {
   // L2-served: the line may sit in this CU's L1 from before an atomic of another wave
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ void raise_flag(int64_t* state, unsigned long long bit) {
-  atomicOr(reinterpret_cast<unsigned long long*>(state + kFlags), bit);
-}
-
-__device__ inline int64_t picks_of(int64_t deg, int64_t k, int replace) {
-  if (k < 0) return deg;
-  if (replace) return deg > 0 ? k : 0;
-  return deg < k ? deg : k;
-}
-
-// start and degree of frontier node v; a node outside the matrix (a bad seed: the flag is
-// up and the call will raise) has no entries.
-__device__ __forceinline__ void row_of(const int64_t* __restrict__ rowptr, int64_t N, int64_t v, int64_t* start,
-                                       int64_t* deg) {
-  if (static_cast<uint64_t>(v) >= static_cast<uint64_t>(N)) {
-    *start = 0;
-    *deg = 0;
-    return;
-  }
-  *start = rowptr[v];
-  *deg = rowptr[v + 1] - *start;
 }
 
 // Slot p picked entry e: claim its column.  Returns e, or -1 for a column outside [0, N).
@@ -87,7 +70,7 @@ __device__ __forceinline__ int64_t claim(const int64_t* __restrict__ col, int64_
                                          int32_t* __restrict__ local, int64_t* __restrict__ state) {
   const int64_t c = col[e];
   if (static_cast<uint64_t>(c) >= static_cast<uint64_t>(N)) {
-    raise_flag(state, kColOutside);
+    raise_flag(state + kFlags, kColOutside);
     return -1;
   }
   __hip_atomic_fetch_max(local + c, static_cast<int32_t>(-2 - p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -107,7 +90,7 @@ neighbor_place_kernel(const int64_t* __restrict__ seeds, int64_t S, int64_t N, i
   if (i >= S) return;
   const int64_t s = seeds[i];
   if (static_cast<uint64_t>(s) >= static_cast<uint64_t>(N)) {
-    raise_flag(state, kSeedOutside);
+    raise_flag(state + kFlags, kSeedOutside);
     return;
   }
   __hip_atomic_fetch_max(local + s, static_cast<int32_t>(i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -120,7 +103,7 @@ neighbor_seed_check_kernel(const int64_t* __restrict__ seeds, int64_t S, int64_t
   if (i >= S) return;
   const int64_t s = seeds[i];
   if (static_cast<uint64_t>(s) >= static_cast<uint64_t>(N)) return;
-  if (ld32(local + s) != static_cast<int32_t>(i)) raise_flag(state, kDupSeed);
+  if (ld32(local + s) != static_cast<int32_t>(i)) raise_flag(state + kFlags, kDupSeed);
 }
 
 __global__ void __launch_bounds__(kThreads)
@@ -155,9 +138,8 @@ neighbor_pick_slot_kernel(const int64_t* __restrict__ rowptr, const int64_t* __r
 }
 
 // Without replacement, deg > k: Floyd's walk exactly as sample_select_floyd_kernel does
-// it, one thread per row.  k <= KMAX: the picks stay in registers (every index is static
-// once the loops are unrolled), so a step does not wait for the previous step's store to
-// come back from memory.
+// it (uniform_pick.h, the draw in [0, j)), one thread per row.  k <= KMAX: the picks stay
+// in registers.
 template <int KMAX>
 __global__ void __launch_bounds__(kThreads)
 neighbor_pick_floyd_reg_kernel(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ col, int64_t N,
@@ -170,18 +152,7 @@ neighbor_pick_floyd_reg_kernel(const int64_t* __restrict__ rowptr, const int64_t
   row_of(rowptr, N, frontier[f], &start, &deg);
   if (deg <= k) return;
   int64_t mine[KMAX];
-  const uint64_t stream = psa::rand_stream(seed, begin + f);
-#pragma unroll
-  for (int t = 0; t < KMAX; ++t) {
-    if (t < k) {
-      const int64_t j = deg - k + t;  // > 0
-      const int64_t pick = start + psa::rand_draw(stream, t, j);
-      bool taken = false;
-#pragma unroll
-      for (int u = 0; u < t; ++u) taken |= mine[u] == pick;
-      mine[t] = taken ? start + j : pick;
-    }
-  }
+  psa::floyd_walk_regs<KMAX, psa::kDrawHalfOpen>(deg, k, psa::rand_stream(seed, begin + f), start, mine);
 #pragma unroll
   for (int t = 0; t < KMAX; ++t)
     if (t < k) e_raw[f * k + t] = claim(col, N, mine[t], f * k + t, local, state);
@@ -198,33 +169,10 @@ neighbor_pick_floyd_kernel(const int64_t* __restrict__ rowptr, const int64_t* __
   row_of(rowptr, N, frontier[f], &start, &deg);
   if (deg <= k) return;
   int64_t* mine = e_raw + f * k;
-  const uint64_t stream = psa::rand_stream(seed, begin + f);
-  for (int64_t t = 0; t < k; ++t) {
-    const int64_t j = deg - k + t;  // > 0
-    int64_t pick = start + psa::rand_draw(stream, t, j);
-    bool taken = false;
-    for (int64_t u = 0; u < t && !taken; ++u) taken = mine[u] == pick;
-    if (taken) pick = start + j;
-    mine[t] = pick;
-  }
+  psa::floyd_walk<psa::kDrawHalfOpen>(deg, k, psa::rand_stream(seed, begin + f), start, mine);
   // claims after the walk: a column outside the matrix turns its slot into -1, which the
   // walk's comparisons must not see
   for (int64_t t = 0; t < k; ++t) mine[t] = claim(col, N, mine[t], f * k + t, local, state);
-}
-
-// Largest r in [lo, hi) with ptr[r] <= p, given ptr[lo] <= p; called by a whole wave.
-__device__ __forceinline__ int64_t wave_search(const int64_t* __restrict__ ptr, int64_t lo, int64_t hi, int64_t p) {
-  const int lane = threadIdx.x & 63;
-  while (hi - lo > 1) {
-    const int64_t step = (hi - lo + 63) / 64;
-    const int64_t x = lo + lane * step;
-    const bool ok = x < hi && ptr[x] <= p;
-    const int cnt = __popcll(__ballot(ok));  // lanes [0, cnt) hold: ptr is non-decreasing
-    const int64_t nhi = lo + cnt * step;
-    lo += (cnt - 1) * step;
-    hi = nhi < hi ? nhi : hi;
-  }
-  return lo;
 }
 
 // k < 0: every stored entry of every frontier row, slot p = fptr[f] + t.  One tile of kTile
@@ -272,13 +220,7 @@ neighbor_pick_all_kernel(const int64_t* __restrict__ rowptr, const int64_t* __re
       r = r_lo + lo;
       base = s_base[lo];
     } else {
-      int64_t lo = r_lo, hi = r_lo + nr;
-      while (hi - lo > 1) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (fptr[mid] <= p) lo = mid;
-        else hi = mid;
-      }
-      r = lo;
+      r = psa::last_le(fptr, r_lo, r_lo + nr, p);
       base = rowptr[frontier[r]] - fptr[r];  // the row has slot p, so the node is inside
     }
     owner[p] = static_cast<int32_t>(r);
@@ -350,10 +292,6 @@ neighbor_reset_kernel(const int64_t* __restrict__ ids, int64_t n, int64_t N, con
     const int64_t e = e_raw[g - n];
     if (e >= 0) local[col[e]] = kUnseen;
   }
-}
-
-unsigned blocks_for(int64_t n, int per = kThreads) {
-  return static_cast<unsigned>(psa::ceil_div(n > 0 ? n : 1, per));
 }
 
 // hop scratch: e_raw int64[cap] | word int64[cap] | ptr int64[cap+1] | owner int32[cap] | count2ptr scratch

@@ -36,11 +36,7 @@
 
 #include <stdint.h>
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define PSA_PPR_FN __host__ __device__ inline
-#else
-#define PSA_PPR_FN inline
-#endif
+#include "rng.h"
 
 namespace psa {
 
@@ -50,24 +46,16 @@ constexpr int64_t kPprTableFull = 1;  // == PSA_PPR_TABLE_FULL
 constexpr int64_t kPprBadIndex = 2;   // == PSA_PPR_BAD_INDEX
 constexpr int64_t kPprInLds = 4;      // == PSA_PPR_IN_LDS
 
-PSA_PPR_FN uint64_t ppr_mulhi(uint64_t a, uint64_t b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __umul64hi(a, b);
-#else
-  return static_cast<uint64_t>((static_cast<unsigned __int128>(a) * b) >> 64);
-#endif
-}
-
 // kPprOne / ((alpha_q * eps_q) >> 32): see the header comment.  alpha_q < 2^32, eps_q <= 2^48.
-PSA_PPR_FN uint64_t ppr_work_bound(uint64_t alpha_q, uint64_t eps_q) {
-  const uint64_t k0 = (ppr_mulhi(alpha_q, eps_q) << 32) | ((alpha_q * eps_q) >> 32);
+PSA_HD uint64_t ppr_work_bound(uint64_t alpha_q, uint64_t eps_q) {
+  const uint64_t k0 = (mulhi64(alpha_q, eps_q) << 32) | ((alpha_q * eps_q) >> 32);
   return k0 ? kPprOne / k0 : kPprOne;
 }
 
 // x >= eps_q * max(deg, 1), without overflow for any deg
-PSA_PPR_FN bool ppr_active(uint64_t x, int64_t deg, uint64_t eps_q) {
+PSA_HD bool ppr_active(uint64_t x, int64_t deg, uint64_t eps_q) {
   const uint64_t d = deg > 0 ? static_cast<uint64_t>(deg) : 1;
-  return ppr_mulhi(eps_q, d) == 0 && x >= eps_q * d;
+  return mulhi64(eps_q, d) == 0 && x >= eps_q * d;
 }
 
 // The split of an active node: what goes to p, what every stored column gets, what stays.
@@ -75,16 +63,16 @@ struct PprSplit {
   uint64_t keep, share, rem;
 };
 
-PSA_PPR_FN PprSplit ppr_split(uint64_t x, int64_t deg, uint64_t alpha_q) {
+PSA_HD PprSplit ppr_split(uint64_t x, int64_t deg, uint64_t alpha_q) {
   if (deg <= 0) return {x, 0, 0};
-  const uint64_t keep = (ppr_mulhi(x, alpha_q) << 32) | ((x * alpha_q) >> 32);
+  const uint64_t keep = (mulhi64(x, alpha_q) << 32) | ((x * alpha_q) >> 32);
   const uint64_t y = x - keep, d = static_cast<uint64_t>(deg);
   const uint64_t share = y / d;
   return {keep, share, y - share * d};
 }
 
 // deg(u) from rowptr, 0 and *flags |= kPprBadIndex when the row's bounds are not inside [0, nnz]
-PSA_PPR_FN int64_t ppr_row(const int64_t* rowptr, int64_t nnz, int64_t u, int64_t* begin, int64_t* flags) {
+PSA_HD int64_t ppr_row(const int64_t* rowptr, int64_t nnz, int64_t u, int64_t* begin, int64_t* flags) {
   const int64_t b = rowptr[u], e = rowptr[u + 1];
   *begin = b;
   if (0 <= b && b <= e && e <= nnz) return e - b;
@@ -92,7 +80,7 @@ PSA_PPR_FN int64_t ppr_row(const int64_t* rowptr, int64_t nnz, int64_t u, int64_
   return 0;
 }
 
-PSA_PPR_FN int64_t ppr_hash(int64_t v, int64_t cap) {
+PSA_HD int64_t ppr_hash(int64_t v, int64_t cap) {
   uint64_t h = static_cast<uint64_t>(v) * 0x9E3779B97F4A7C15ull;
   h ^= h >> 32;
   return static_cast<int64_t>(h & static_cast<uint64_t>(cap - 1));
@@ -101,7 +89,7 @@ PSA_PPR_FN int64_t ppr_hash(int64_t v, int64_t cap) {
 // The largest i in [0, n) with scan[i] <= e, scan non-decreasing with scan[0] = 0 <= e < scan[n]:
 // the node of a chunk that owns entry number e.  At most 64 halvings.
 template <typename Scan>
-PSA_PPR_FN int ppr_owner(const Scan* scan, int n, int64_t e) {
+PSA_HD int ppr_owner(const Scan* scan, int n, int64_t e) {
   int lo = 0, hi = n;  // the answer is in [lo, hi)
   for (int i = 0; i < 64 && hi - lo > 1; ++i) {
     const int mid = lo + ((hi - lo) >> 1);
@@ -128,7 +116,7 @@ struct PprHostMem {
 // node (nothing is touched) or kPprTableFull when cap probes found neither v nor a free slot
 // (the add is dropped).  No slot outside [0, cap) is ever addressed.
 template <typename M>
-PSA_PPR_FN int64_t ppr_add(int64_t* key, uint64_t* r, uint64_t* p, uint64_t* s, int64_t cap, int64_t N, int64_t v,
+PSA_HD int64_t ppr_add(int64_t* key, uint64_t* r, uint64_t* p, uint64_t* s, int64_t cap, int64_t N, int64_t v,
                            uint64_t share) {
   if (v < 0 || v >= N) return kPprBadIndex;
   int64_t slot = ppr_hash(v, cap);

@@ -24,6 +24,7 @@
 // this file waits for another one.  Every loop is bounded by N or nnz.
 #include "coalesce_internal.h"
 #include "common.h"
+#include "search.h"
 
 namespace {
 
@@ -275,20 +276,7 @@ rcm_small_kernel(const int64_t* __restrict__ rowptr, const int64_t* __restrict__
 
 // ---- large path -----------------------------------------------------------------------
 
-// Largest r in [lo, hi) with ptr[r] <= p, given ptr[lo] <= p; called by a whole wave.
-__device__ __forceinline__ int64_t wave_search(const int64_t* __restrict__ ptr, int64_t lo, int64_t hi, int64_t p) {
-  const int lane = threadIdx.x & 63;
-  while (hi - lo > 1) {
-    const int64_t step = (hi - lo + 63) / 64;
-    const int64_t x = lo + lane * step;
-    const bool ok = x < hi && ptr[x] <= p;
-    const int cnt = __popcll(__ballot(ok));  // lanes [0, cnt) hold: ptr is non-decreasing
-    const int64_t nhi = lo + cnt * step;
-    lo += (cnt - 1) * step;
-    hi = nhi < hi ? nhi : hi;
-  }
-  return lo;
-}
+using psa::wave_search;
 
 __global__ void __launch_bounds__(kThreads)
 rcm_frontier_deg_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ order, int64_t lo, int64_t F,
@@ -551,7 +539,7 @@ int rcm_args(const char* who, int64_t N, int64_t nnz, const void* workspace, siz
   return PSA_OK;
 }
 
-unsigned blocks_for(int64_t n) { return static_cast<unsigned>(psa::ceil_div(n > 0 ? n : 1, kThreads)); }
+using psa::blocks_for;
 
 }  // namespace
 

@@ -20,20 +20,16 @@
 // reproduces them bit for bit.  (The reference draws from Paddle's global
 // generator, which no other implementation can reproduce.)
 #include "common.h"
-#include "rng.h"
+#include "uniform_pick.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int64_t kUnseen = INT64_MIN;
 
+using psa::grid_for;
+using psa::picks_of;
 using psa::randint;
-
-__device__ inline int64_t picks_of(int64_t deg, int64_t k, int replace) {
-  if (k < 0) return deg;                       // sample_cpu.cpp:45-63
-  if (replace) return deg > 0 ? k : 0;         // :66-88
-  return deg < k ? deg : k;                    // :90-121
-}
 
 __global__ void __launch_bounds__(kThreads)
 sample_count_kernel(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ idx,
@@ -63,10 +59,9 @@ sample_select_slot_kernel(const int64_t* __restrict__ rowptr, const int64_t* __r
   }  // else: a Floyd row, written by sample_select_floyd_kernel
 }
 
-// Without replacement, deg > k (sample_cpu.cpp:100-106): for j = deg-k .. deg-1
-// draw r in [0, j); take r unless already taken, then take j.  One thread per
-// row; picks are kept in draw order in the row's own output slots, which double
-// as the "already taken" set (k is small: the scan is k^2 / 2 compares).
+// Without replacement, deg > k (sample_cpu.cpp:100-106): Floyd's walk of uniform_pick.h
+// with upstream's draw in [0, j).  One thread per row; picks are kept in draw order in
+// the row's own output slots, which double as the "already taken" set.
 __global__ void __launch_bounds__(kThreads)
 sample_select_floyd_kernel(const int64_t* __restrict__ rowptr, const int64_t* __restrict__ idx,
                            const int64_t* __restrict__ out_rowptr, int64_t S, int64_t k,
@@ -76,15 +71,7 @@ sample_select_floyd_kernel(const int64_t* __restrict__ rowptr, const int64_t* __
   const int64_t n = idx[i];
   const int64_t start = rowptr[n], deg = rowptr[n + 1] - start;
   if (deg <= k) return;
-  int64_t* mine = e_raw + out_rowptr[i];
-  for (int64_t t = 0; t < k; ++t) {
-    const int64_t j = deg - k + t;
-    int64_t pick = start + (j > 0 ? randint(seed, i, t, j) : 0);
-    bool taken = j == 0;
-    for (int64_t u = 0; u < t && !taken; ++u) taken = mine[u] == pick;
-    if (taken) pick = start + j;
-    mine[t] = pick;
-  }
+  psa::floyd_walk<psa::kDrawHalfOpen>(deg, k, psa::rand_stream(seed, i), start, e_raw + out_rowptr[i]);
 }
 
 __global__ void __launch_bounds__(kThreads)
@@ -140,13 +127,6 @@ relabel_finish_kernel(const int64_t* __restrict__ idx, int64_t S,
     }
     keys[p] = owner[p] * n_out + id;
   }
-}
-
-int grid_for(int64_t n, unsigned* blocks) {
-  const int64_t b = psa::ceil_div(n > 0 ? n : 1, kThreads);
-  if (b > 0x7fffffff) return 0;
-  *blocks = static_cast<unsigned>(b);
-  return 1;
 }
 
 }  // namespace

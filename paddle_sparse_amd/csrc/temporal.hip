@@ -8,7 +8,8 @@
 // positions of row v ascending by (time, position) and sorted_time their times.  The eligible
 // set of (v, T) is therefore a prefix of the row's segment, c entries long, found by one
 // upper-bound search; a pick is a rank in [0, c) and one load of `order`.  The rules that turn
-// (c, k, replace, strategy, stream) into ranks are temporal_pick.h, shared with the host export.
+// (c, k, replace, strategy, stream) into ranks are temporal_pick.h over uniform_pick.h's Floyd
+// walk, shared with the host export; the searches in scanned counts and node lists are search.h's.
 //
 // Walk list, streams and slot numbering are ego.hip's: entry i < S is seed i of ego i, hop l
 // expands every entry of hop l - 1, the parent at walk index i draws on stream i, a hop with
@@ -31,18 +32,19 @@
 // flag word, no workgroup waits for another, every loop is bounded by k or a log; every index
 // read from memory is checked against its array before it is used as one.
 #include "common.h"
+#include "search.h"
 #include "temporal_pick.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kFloydRegs = 32;
-constexpr int64_t kMaxSlots = 0x7ffffff0;
 constexpr unsigned long long kColOutside = PSA_EGO_COL_OUTSIDE, kBadIndex = PSA_TEMPORAL_BAD_INDEX;
 
-__device__ __forceinline__ void raise_flag(int64_t* flags, unsigned long long bit) {
-  atomicOr(reinterpret_cast<unsigned long long*>(flags), bit);
-}
+using psa::blocks_for;
+using psa::first_equal;
+using psa::kFloydRegs;
+using psa::kMaxSlots;
+using psa::raise_flag;
 
 struct Graph {
   const int64_t* __restrict__ rowptr;
@@ -132,7 +134,7 @@ temporal_pick_slot_kernel(Graph G, const int64_t* __restrict__ pnode, const int3
   if (psa::temporal_is_floyd(c, k, replace, strategy)) return;
   int64_t at = -1;
   if (t < psa::temporal_picks_of(c, k, replace, strategy))
-    at = start + psa::temporal_slot_rank(c, replace, strategy, psa::temporal_stream(seed, begin + f), t);
+    at = start + psa::temporal_slot_rank(c, replace, strategy, psa::rand_stream(seed, begin + f), t);
   emit(G, at, g, p, node_out, key_out, ekey_out, flags);
 }
 
@@ -151,7 +153,7 @@ temporal_pick_floyd_reg_kernel(Graph G, const int64_t* __restrict__ pnode, const
   const int64_t c = eligible(G, start, deg, g);
   if (c <= k) return;
   int64_t mine[KMAX];
-  psa::temporal_floyd_small<KMAX>(c, k, psa::temporal_stream(seed, begin + f), mine);
+  psa::floyd_walk_regs<KMAX, psa::kDrawClosed>(c, k, psa::rand_stream(seed, begin + f), 0, mine);
 #pragma unroll
   for (int t = 0; t < KMAX; ++t)
     if (t < k) emit(G, start + mine[t], g, f * k + t, node_out, key_out, ekey_out, flags);
@@ -170,7 +172,7 @@ temporal_pick_floyd_kernel(Graph G, const int64_t* __restrict__ pnode, const int
   const int64_t c = eligible(G, start, deg, g);
   if (c <= k) return;
   int64_t* mine = node_out + f * k;
-  psa::temporal_floyd_large(c, k, psa::temporal_stream(seed, begin + f), mine);
+  psa::floyd_walk<psa::kDrawClosed>(c, k, psa::rand_stream(seed, begin + f), 0, mine);
   // ranks become nodes after the walk, whose comparisons must see ranks only
   for (int64_t t = 0; t < k; ++t) emit(G, start + mine[t], g, f * k + t, node_out, key_out, ekey_out, flags);
 }
@@ -183,12 +185,7 @@ temporal_pick_all_kernel(Graph G, const int64_t* __restrict__ pnode, const int32
                          int64_t* __restrict__ flags) {
   const int64_t p = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
   if (p >= cap) return;
-  int64_t lo = 0, hi = F;  // pptr[0] = 0 <= p < cap = pptr[F]
-  for (int i = 0; i < 64 && hi - lo > 1; ++i) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (pptr[mid] <= p) lo = mid;
-    else hi = mid;
-  }
+  const int64_t lo = psa::last_le(pptr, 0, F, p);  // pptr[0] = 0 <= p < cap = pptr[F]
   const int32_t g = pego[lo];
   ego_out[p] = g;
   int64_t start, deg;
@@ -205,24 +202,13 @@ __global__ void temporal_total_kernel(const int64_t* __restrict__ count_words, c
   state[2] = *flags;
 }
 
-// position of x in the ascending list[lo0, hi0), or -1
-__device__ __forceinline__ int64_t find(const int64_t* __restrict__ list, int64_t lo0, int64_t hi0, int64_t x) {
-  int64_t lo = lo0, hi = hi0;
-  for (int i = 0; i < 64 && lo < hi; ++i) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (list[mid] < x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < hi0 && list[lo] == x ? lo : -1;
-}
-
 __global__ void __launch_bounds__(kThreads)
 temporal_root_kernel(const int64_t* __restrict__ n_id, const int64_t* __restrict__ ptr, int64_t n,
                      const int64_t* __restrict__ seeds, int64_t S, int64_t* __restrict__ root) {
   const int64_t g = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x;
   if (g >= S) return;
   const int64_t first = ptr[g], end = ptr[g + 1];
-  root[g] = first >= 0 && first <= end && end <= n ? find(n_id, first, end, seeds[g]) : -1;
+  root[g] = first >= 0 && first <= end && end <= n ? first_equal(n_id, first, end, seeds[g]) : -1;
 }
 
 // One thread per distinct edge key (g, e), q < m: the sentinel sorts behind them.
@@ -237,16 +223,11 @@ temporal_finish_kernel(const int64_t* __restrict__ rowptr, const int64_t* __rest
   const int64_t g = key_ego[q], e = key_edge[q];
   int64_t r = -1, c = -1;
   if (static_cast<uint64_t>(g) < static_cast<uint64_t>(S) && static_cast<uint64_t>(e) < static_cast<uint64_t>(nnz)) {
-    int64_t lo = 0, hi = N;  // the row of e: the largest v with rowptr[v] <= e (rowptr[0] = 0)
-    for (int i = 0; i < 64 && hi - lo > 1; ++i) {
-      const int64_t mid = lo + ((hi - lo) >> 1);
-      if (rowptr[mid] <= e) lo = mid;
-      else hi = mid;
-    }
+    const int64_t v = psa::last_le(rowptr, 0, N, e);  // the row of e (rowptr[0] = 0)
     const int64_t first = ptr[g], end = ptr[g + 1];
     if (first >= 0 && first <= end && end <= n) {
-      r = find(n_id, first, end, lo);
-      c = find(n_id, first, end, col[e]);  // a column outside [0, N) is no node of the set
+      r = first_equal(n_id, first, end, v);
+      c = first_equal(n_id, first, end, col[e]);  // a column outside [0, N) is no node of the set
     }
   }
   if (r < 0 || c < 0) {  // the pick kernels emitted both nodes: never, unless the inputs changed under the op
@@ -257,8 +238,6 @@ temporal_finish_kernel(const int64_t* __restrict__ rowptr, const int64_t* __rest
   col_out[q] = c;
   edge_out[q] = e;
 }
-
-unsigned blocks_for(int64_t n) { return static_cast<unsigned>(psa::ceil_div(n > 0 ? n : 1, kThreads)); }
 
 bool key_range(int64_t S, int64_t N, int64_t nnz) {
   if (S < 0 || N < 0 || nnz < 0 || S >= (int64_t{1} << 31)) return false;
@@ -361,15 +340,15 @@ int64_t psa_temporal_pick_host(const int64_t* sorted_time, int64_t start, int64_
     for (int64_t t = 0; t < c; ++t) ranks[t] = t;
     return count;
   }
-  const uint64_t stream = psa::temporal_stream(seed, stream_index);
+  const uint64_t stream = psa::rand_stream(seed, stream_index);
   if (!psa::temporal_is_floyd(c, k, replace, strategy)) {
     for (int64_t t = 0; t < count; ++t) ranks[t] = psa::temporal_slot_rank(c, replace, strategy, stream, t);
   } else if (k <= kFloydRegs) {  // the two walks the kernels run, chosen as they choose
     int64_t mine[kFloydRegs];
-    psa::temporal_floyd_small<kFloydRegs>(c, k, stream, mine);
+    psa::floyd_walk_regs<kFloydRegs, psa::kDrawClosed>(c, k, stream, 0, mine);
     for (int64_t t = 0; t < k; ++t) ranks[t] = mine[t];
   } else {
-    psa::temporal_floyd_large(c, k, stream, ranks);
+    psa::floyd_walk<psa::kDrawClosed>(c, k, stream, 0, ranks);
   }
   return count;
 }

@@ -19,7 +19,7 @@
 //                   psa_count2ptr -> in_ptr (C = in_ptr[S] candidates)
 //   tile count      a fixed grid of kBlocks workgroups splits [0, C) evenly (C
 //                   is read on the device, so no host read sizes the grid); a
-//                   tile finds the rows it spans by a wave search in in_ptr and
+//                   tile finds the rows it spans by search.h's wave search in in_ptr and
 //                   stages them in LDS as diag.hip's write pass does; candidate
 //                   p of row i is entry e = rowptr[node_idx[i]] + p - in_ptr[i],
 //                   kept when assoc[col[e]] >= 0.  A hub row spans many tiles.
@@ -31,6 +31,7 @@
 // (flag bit 2); only then does the caller re-sort.
 #include "common.h"
 #include "rng.h"
+#include "search.h"
 
 namespace {
 
@@ -103,30 +104,8 @@ random_walk_kernel(const int64_t* __restrict__ rowptr, const int64_t* __restrict
 
 // ---- saint_subgraph ---------------------------------------------------------------
 
-// Largest r in [lo, hi) with ptr[r] <= p, given ptr[lo] <= p; called by a whole wave.
-__device__ __forceinline__ int64_t wave_search(const int64_t* __restrict__ ptr, int64_t lo, int64_t hi, int64_t p) {
-  const int lane = threadIdx.x & 63;
-  while (hi - lo > 1) {
-    const int64_t step = (hi - lo + 63) / 64;
-    const int64_t x = lo + lane * step;
-    const bool ok = x < hi && ptr[x] <= p;
-    const int cnt = __popcll(__ballot(ok));  // lanes [0, cnt) hold: ptr is non-decreasing
-    const int64_t nhi = lo + cnt * step;
-    lo += (cnt - 1) * step;
-    hi = nhi < hi ? nhi : hi;
-  }
-  return lo;
-}
-
-// Largest r in [lo, hi) with ptr[r] <= p (ptr[lo] <= p), one lane.
-__device__ __forceinline__ int64_t last_le(const int64_t* __restrict__ ptr, int64_t lo, int64_t hi, int64_t p) {
-  while (hi - lo > 1) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (ptr[mid] <= p) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
+using psa::last_le;
+using psa::wave_search;
 
 __global__ void __launch_bounds__(kThreads)
 saint_init_kernel(int64_t* __restrict__ assoc, int64_t N, unsigned long long* __restrict__ info) {
@@ -308,12 +287,7 @@ saint_write_kernel(const int64_t* __restrict__ rowptr, const int64_t* __restrict
   }
 }
 
-int grid_for(int64_t n, unsigned* blocks) {
-  const int64_t b = psa::ceil_div(n > 0 ? n : 1, kThreads);
-  if (b > 0x7fffffff) return 0;
-  *blocks = static_cast<unsigned>(b);
-  return 1;
-}
+using psa::grid_for;
 
 // workspace: assoc int64[N] | counts int64[S] | in_ptr int64[S+1] | block_counts int64[kBlocks]
 //            | block_ptr int64[kBlocks+1] | count2ptr scratch (max of S and kBlocks)

@@ -227,12 +227,7 @@ sample_select_weighted_kernel(const int64_t* __restrict__ rowptr, const double* 
   }
 }
 
-int grid_for(int64_t n, unsigned* blocks) {
-  const int64_t b = psa::ceil_div(n > 0 ? n : 1, kThreads);
-  if (b > 0x7fffffff) return 0;
-  *blocks = static_cast<unsigned>(b);
-  return 1;
-}
+using psa::grid_for;
 
 }  // namespace
 

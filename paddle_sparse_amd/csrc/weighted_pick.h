@@ -14,16 +14,12 @@
 
 #include <stdint.h>
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define PSA_PICK_FN __host__ __device__ inline
-#else
-#define PSA_PICK_FN inline
-#endif
+#include "rng.h"
 
 namespace psa {
 
 // Index in [0, deg) of the pick (deg > 0), or -1 when the row's total is not positive.
-PSA_PICK_FN int64_t weighted_pick(const double* cum, int64_t deg, uint64_t r) {
+PSA_HD int64_t weighted_pick(const double* cum, int64_t deg, uint64_t r) {
 #if defined(__clang__)
 #pragma clang fp contract(off)  // target is a product rounded once, never part of an fma
 #endif
@@ -67,13 +63,13 @@ namespace psa {
 struct PickWordArrays {
   const uint64_t* entry_words;
   const uint64_t* gap_words;
-  PSA_PICK_FN uint64_t entry(int64_t t) const { return entry_words[t]; }
-  PSA_PICK_FN uint64_t gap(int64_t t) const { return gap_words[t]; }
+  PSA_HD uint64_t entry(int64_t t) const { return entry_words[t]; }
+  PSA_HD uint64_t gap(int64_t t) const { return gap_words[t]; }
 };
 
 // Stage 2: the pick among positions [lo, hi) of the row, base = cum[lo - 1] (0.0 for lo == 0),
 // top = cum[hi - 1], mass = top - base > 0.
-PSA_PICK_FN int64_t weighted_pick_gap(const double* cum, int64_t lo0, int64_t hi0, double base, double top,
+PSA_HD int64_t weighted_pick_gap(const double* cum, int64_t lo0, int64_t hi0, double base, double top,
                                       double mass, uint64_t r) {
 #if defined(__clang__)
 #pragma clang fp contract(off)  // one rounded multiply, then one rounded add
@@ -98,7 +94,7 @@ PSA_PICK_FN int64_t weighted_pick_gap(const double* cum, int64_t lo0, int64_t hi
 }
 
 // The stage-1 target of draw t: u1 * total, one rounded multiply.
-PSA_PICK_FN double weighted_gap_target(double total, uint64_t r1) {
+PSA_HD double weighted_gap_target(double total, uint64_t r1) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -112,7 +108,7 @@ PSA_PICK_FN double weighted_gap_target(double total, uint64_t r1) {
 // device); inserting a pick splits one mass in two, which gives the bits a fresh difference
 // of the gap's ends would give.
 template <int KMAX, class Words>
-PSA_PICK_FN int64_t weighted_pick_without_small(const double* cum, int64_t deg, int64_t k, const Words& words,
+PSA_HD int64_t weighted_pick_without_small(const double* cum, int64_t deg, int64_t k, const Words& words,
                                                 int64_t* out) {
   int32_t taken[KMAX];     // ascending, [0, n)
   double mass[KMAX + 1];   // of gap g = (taken[g-1], taken[g]), [0, n]
@@ -177,7 +173,7 @@ PSA_PICK_FN int64_t weighted_pick_without_small(const double* cum, int64_t deg, 
 // Any k >= 1 and any deg: the ascending view of the taken positions lives in sorted[0 .. k)
 // (memory of the caller), the masses are differences read afresh at every draw.
 template <class Words>
-PSA_PICK_FN int64_t weighted_pick_without_large(const double* cum, int64_t deg, int64_t k, const Words& words,
+PSA_HD int64_t weighted_pick_without_large(const double* cum, int64_t deg, int64_t k, const Words& words,
                                                 int64_t* sorted, int64_t* out) {
   int64_t n = 0;
   for (; n < k; ++n) {
