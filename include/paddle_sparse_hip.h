@@ -1722,6 +1722,47 @@ int psa_ppr_host(const int64_t* rowptr, const int64_t* col, int64_t N, int64_t n
                  int64_t cap, uint64_t alpha_q, uint64_t eps_q, int64_t max_rounds, int64_t* table_key,
                  uint64_t* table_r, uint64_t* table_p, uint64_t* table_s, int64_t* info);
 
+/* ---- multi-aggregation SpMM: several statistics of the same neighbourhood from one gather, fp32.
+ * Operands as psa_spmm: rowptr int64[M + 1], col int64[nnz] in [0, N), value f32[nnz] or NULL (ones),
+ * mat f32[N, K] row-major.  With m_e = value[e] * mat[col[e], :] and n = the stored entries of row r:
+ *   PSA_SUM   sum of m                    PSA_MEAN  sum / n
+ *   PSA_MIN / PSA_MAX  psa_spmm's rule, NaN and +-inf included (a product must beat +-FLT_MAX
+ *             strictly to win, so a NaN never does; the first winner in entry order) and its bits,
+ *             with psa_spmm's own exception: where +0 and -0 tie for the extreme, which of the two
+ *             zeros is stored depends on the kernel that ran and on whether winners are tracked
+ *             (the value compares equal either way; the winner is the first of the tied entries)
+ *   PSA_VAR   max(sum of m^2 / n - mean^2, 0), the population variance
+ *   PSA_STD   sqrt(var + eps), eps >= 0
+ * A row without entries is 0 in every statistic.  `stats` is the bit set (1 << code) of the wanted
+ * statistics; `order` is a HOST array of the same A codes, each once: out f32[M, A, K] holds
+ * statistic order[a] of row r at out[r, a, :], and is fully written.  arg_min / arg_max: int64[M, K]
+ * or NULL, the entry id of the first winner (nnz: none); wanted for the backward only, and allowed
+ * only with the statistic in the set.  mean_out: f32[M, K] or NULL, the mean once more outside out,
+ * for a backward of var / std whose call does not name the mean (allowed with any of sum, mean, var,
+ * std in the set: one more tile written, nothing more kept).  What the kernels keep per lane is compiled per set: a
+ * statistic that is not wanted costs no registers, shuffles or stores, and the winners are tracked
+ * only when an arg array is given.
+ * One wave per row gathers every row of mat once; K % 4 == 0 with 16-byte aligned mat, out and arg
+ * arrays takes 16-byte gathers, anything else 4-byte loads (any K >= 1).  workspace (16-byte
+ * aligned; not needed when nnz <= 128) enables the long-row path: rows above 128 entries run as
+ * 128-entry chunks whose partials are folded in chunk order.  It is the list and P four-byte
+ * partial rows of K per chunk, psa_spmm_heads_workspace_bytes(nnz, P, K) bytes, with P = one row
+ * each for the sum (sum, mean, var or std wanted), the sum of squares (var or std), min and max,
+ * and, when an arg array is given, one more for each of min and max in the set.
+ * workspace == NULL keeps every row on one wave: the same
+ * semantics, for callers that know that no row is long (such a row must stay below 2^31 entries).
+ * No float atomics, no host read: bitwise reproducible and capturable.  PSA_ERR_INVALID_ARG: a
+ * negative size, A outside [1, 6], an unknown or repeated code, order and stats that disagree, an
+ * arg array without its statistic, eps < 0 or NaN, a NULL required pointer. */
+typedef enum psa_stat { /* the first four are psa_reduce's codes */
+  PSA_VAR = 4,
+  PSA_STD = 5
+} psa_stat;
+int psa_spmm_multi(const int64_t* rowptr, const int64_t* col, const float* value, const float* mat, int64_t M,
+                   int64_t N, int64_t K, int64_t nnz, int stats, float eps, const int* order, int64_t A, float* out,
+                   int64_t* arg_min, int64_t* arg_max, float* mean_out, void* workspace, size_t workspace_bytes,
+                   psa_stream_t stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -77,6 +77,7 @@ if not _running_the_builder():
         ("components", ("connected_components", "largest_connected_components")),
         ("topk", ("topk", "segment_topk")),
         ("ppr", ("ppr",)),
+        ("multi_aggr", ("spmm_multi",)),
     )
 
     __all__ = ["__version__"]

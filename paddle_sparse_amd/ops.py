@@ -12,6 +12,7 @@ CPU tensors are rejected: this build has no CPU kernels and never falls back.
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from typing import List, Optional, Tuple
 
@@ -311,6 +312,115 @@ def csr_row_stats(rowptr: torch.Tensor) -> Tuple[int, int, int, int]:
 def spmm_set_variant(variant: int) -> int:
     """Bench/test hook: pick the SpMM kernel variant (0 = auto)."""
     return _lib.load().psa_spmm_set_variant(int(variant))
+
+
+# ---- multi-aggregation SpMM: several statistics from one gather (csrc/spmm_multi.hip) ---------------
+
+STAT_ID = {"sum": 0, "add": 0, "mean": 1, "min": 2, "max": 3, "var": 4, "std": 5}  # psa_reduce / psa_stat
+# floats of one K tile: 64 lanes x 16 bytes when K % 4 == 0 (16-byte gathers), 64 lanes x 4 bytes otherwise
+SPMM_MULTI_TILE_VEC4 = 256
+SPMM_MULTI_TILE_SCALAR = 64
+SPMM_MULTI_MIN_LANES = 4      # fewest lanes per entry: at most 64 // 4 entries share a wave instruction
+SPMM_MULTI_STEPS = 4          # such steps in flight before the first is consumed
+SPMM_MULTI_CHUNK_WAVES = 2048 * 4  # waves of the capped chunk / combine grids: more chunks take a second trip
+
+
+def spmm_multi_lanes(K: int, vec4: Optional[bool] = None) -> int:
+    """Lanes per entry the launch picks for width K: the power of two >= K / 4 (K % 4 == 0) or >= K, within [4, 64]."""
+    q = K // 4 if (K % 4 == 0 if vec4 is None else vec4) else K
+    lanes = SPMM_MULTI_MIN_LANES
+    while lanes < 64 and lanes < q:
+        lanes *= 2
+    return lanes
+
+
+def spmm_multi_stats(reduce) -> Tuple[int, ...]:
+    """The statistic codes of `reduce`, a non-empty sequence of distinct names out of sum (add), mean, min, max,
+    var, std; ValueError otherwise."""
+    if isinstance(reduce, str) or not hasattr(reduce, "__iter__"):
+        raise ValueError(f"reduce must be a sequence of statistic names (got {reduce!r})")
+    names = list(reduce)
+    if not names:
+        raise ValueError("reduce must name at least one statistic")
+    codes = []
+    for name in names:
+        if name not in STAT_ID:
+            raise ValueError(f"unknown statistic {name!r}: choose from sum (add), mean, min, max, var, std")
+        if STAT_ID[name] in codes:
+            raise ValueError(f"statistic {name!r} is named twice")
+        codes.append(STAT_ID[name])
+    return tuple(codes)
+
+
+def spmm_multi_partials(codes, want_arg: bool) -> int:
+    """Four-byte partial rows a chunk of a long row leaves (include/paddle_sparse_hip.h, psa_spmm_multi): the sum, the
+    sum of squares, min, max, and with want_arg the winners of those of min / max that are in the set."""
+    sums = any(c in codes for c in (0, 1, 4, 5)) + any(c in codes for c in (4, 5))
+    extremes = (2 in codes) + (3 in codes)
+    return sums + extremes * (2 if want_arg else 1)
+
+
+def spmm_multi(rowptr: torch.Tensor, col: torch.Tensor, value: Optional[torch.Tensor], mat: torch.Tensor, reduce,
+               eps: float = 1e-5, want_arg: bool = False, no_long_rows: bool = False,
+               out: Optional[torch.Tensor] = None, want_mean: bool = False):
+    """(out f32[M, A, K], arg_min | None, arg_max | None): out[:, a] = statistic reduce[a] of the messages
+    value[e] * mat[col[e]] of every row, all from ONE gather of mat (psa_spmm_multi).  want_arg: also the int64
+    [M, K] first winners of min / max, for those of the two that are in `reduce` (nnz: no winner).  no_long_rows:
+    the caller knows that no row has more than LONG_ROW entries (SparseStorage._longest_row); no workspace is then
+    brought and the chunk and combine launches are skipped.  `out`: a contiguous f32 [M, A, K] tensor to fill
+    (test hook: starts poisoned).  want_mean (with any of sum, mean, var, std in `reduce`): a fourth result, the mean
+    f32 [M, K] once more outside `out`, for a backward of var / std whose `reduce` does not name it."""
+    rowptr, col = _index(rowptr, "rowptr"), _index(col, "col")
+    _gpu(mat, "mat")
+    if mat.dtype in (torch.float16, torch.bfloat16):
+        raise TypeError(f"spmm_multi takes a float32 dense operand; half-width operands are not built yet (mat is {mat.dtype})")
+    if mat.dtype != torch.float32:
+        raise TypeError(f"spmm_multi takes a float32 dense operand (mat is {mat.dtype})")
+    if mat.dim() != 2:
+        raise ValueError(f"spmm_multi takes a 2-D dense operand [N, K]; [N, H, F] operands are not built yet (got {tuple(mat.shape)})")
+    if value is not None:
+        _gpu(value, "value")
+        if value.dtype != torch.float32 or value.dim() != 1 or value.numel() != col.numel():
+            raise ValueError("value must be float32[nnz]")
+        value = value.contiguous()
+    if rowptr.numel() < 1:
+        raise ValueError("rowptr must have at least one element")
+    codes = spmm_multi_stats(reduce)
+    eps = float(eps)
+    if not eps >= 0.0:
+        raise ValueError(f"eps must be a float >= 0 (got {eps})")
+    mat = mat.contiguous()
+    M, (N, K), nnz, A = rowptr.numel() - 1, mat.shape, col.numel(), len(codes)
+    if K % 4 == 0:
+        mat = _aligned16(mat)
+    if out is None:
+        out = torch.empty((M, A, K), dtype=torch.float32, device=mat.device)
+    elif out.dtype != torch.float32 or out.shape != (M, A, K) or not out.is_contiguous() or out.device != mat.device:
+        raise ValueError(f"out must be a contiguous float32 [{M}, {A}, {K}] tensor on mat's device")
+    arg_min = arg_max = None
+    if want_arg and STAT_ID["min"] in codes:
+        arg_min = torch.empty((M, K), dtype=torch.int64, device=mat.device)
+    if want_arg and STAT_ID["max"] in codes:
+        arg_max = torch.empty((M, K), dtype=torch.int64, device=mat.device)
+    stats = 0
+    for c in codes:
+        stats |= 1 << c
+    mean = None
+    if want_mean:
+        if not any(c in codes for c in (0, 1, 4, 5)):
+            raise ValueError("want_mean needs one of sum, mean, var, std in reduce")
+        mean = torch.empty((M, K), dtype=torch.float32, device=mat.device)
+    order = (ctypes.c_int * A)(*codes)
+    lib = _lib.load()
+    ws_bytes = 0 if no_long_rows else lib.psa_spmm_heads_workspace_bytes(nnz, spmm_multi_partials(codes, want_arg), K)
+    ws = _workspace(ws_bytes, mat.device) if ws_bytes else None
+    with _on(mat.device):
+        check(lib.psa_spmm_multi(_ptr(rowptr), _ptr(col), _ptr(value), _ptr(mat), M, N, K, nnz, stats, eps,
+                                 ctypes.addressof(order), A, _ptr(out), _ptr(arg_min), _ptr(arg_max), _ptr(mean), _ptr(ws),
+                                 ws_bytes, _stream()))
+    if want_mean:
+        return out, arg_min, arg_max, mean
+    return out, arg_min, arg_max
 
 
 # ---------------------------------------------------------------------------
