@@ -1763,6 +1763,44 @@ int psa_spmm_multi(const int64_t* rowptr, const int64_t* col, const float* value
                    int64_t* arg_min, int64_t* arg_max, float* mean_out, void* workspace, size_t workspace_bytes,
                    psa_stream_t stream);
 
+/* ---- segment_matmul: per-type weights over row segments, on MFMA, fp32 and bf16.
+ * Rows are sorted by type: ptr int64[T + 1], non-decreasing, ptr[0] = 0, ptr[T] = R, and for ptr[t] <= r < ptr[t + 1]
+ *   out_row(r) = x_row(r) @ weight[t]
+ * x_row(r) = x[index[r]] (index int64[R]) or x[r] (index NULL, then Nx == R); out_row(r) = out[out_index[r]]
+ * (out_index int64[R]) or out[r] (NULL).  out_index MUST be injective (a permutation of [0, R)): two rows with the
+ * same target would race; this is not checked.  x [Nx, K], weight [T, K, F], or with trans_w != 0 [T, F, K] read
+ * transposed (the product of the gradient wrt x), out [R, F]: row-major, contiguous, of `dtype` PSA_F32 or PSA_BF16
+ * (anything else: PSA_ERR_INVALID_ARG).  bf16 accumulates in fp32 and rounds once, to nearest even, where out is
+ * written.  Any K, F >= 1 and any element alignment: K % 4 == 0 and F % 4 == 0 (bf16: % 8) with 16-byte aligned x
+ * and weight take 16-byte loads, anything else element loads.  ptr, index and out_index are trusted: no range check.
+ * tile_ptr: int64[T + 1] of the caller's, written by the call (the first row tile of every segment; a tile is
+ * 64 rows of ONE segment times 64 columns).  The tile map is made on the device and the grid is the bound
+ * ceil(R / 64) + T row tiles, so there is no host read: capturable.  One writer and one summation order per
+ * element, no atomics: the same bits on every run.
+ * Non-finite values: a NaN or inf in x_row(r) reaches out_row(r) only, one in weight[t] the rows of segment t only
+ * (the K tail of BOTH operands is filled with zeros, so a padded 0 never meets a stray inf).
+ * Never read: x rows that no index names, weight[t] of an empty segment, anything when R == 0 or T == 0 (PSA_OK,
+ * nothing launched, out untouched).  Never written: out rows that no out_index names.
+ *
+ * psa_segment_matmul_bw_weight: grad_weight[t] [K, F] = sum over the rows r of segment t of
+ * x_row(r)^T (outer) grad_row(r), grad_row(r) = grad[out_index[r]] or grad[r]; grad [R, F], grad_weight [T, K, F] of
+ * `dtype`, fully written (zeros for an empty segment).  The rows are the reduction dimension of the MFMA.  A segment
+ * of at most CH rows writes grad_weight[t] directly; a longer one runs as CH-row chunks whose fp32 partial products
+ * go to `partial` and are folded in chunk order by a second kernel (no float atomics: reproducible).
+ * chunk_ptr: int64[2 * (T + 1)] of the caller's (the device-made chunk map); partial: fp32
+ * [partial_chunks, K, F] with partial_chunks >= psa_segment_matmul_bw_chunks(R) = 2 * ceil(R / CH), a bound on the
+ * chunks of all long segments (PSA_ERR_INVALID_ARG below it; NULL allowed when it is 0).  Capturable.
+ * psa_segment_matmul_tile: the constants BM, BN (tile), BK (reduction step) and CH. */
+int psa_segment_matmul(int dtype, const void* x, const int64_t* index, const int64_t* ptr, const void* weight,
+                       const int64_t* out_index, int64_t Nx, int64_t R, int64_t T, int64_t K, int64_t F, int trans_w,
+                       int64_t* tile_ptr, void* out, psa_stream_t stream);
+int psa_segment_matmul_bw_weight(int dtype, const void* x, const int64_t* index, const void* grad,
+                                 const int64_t* out_index, const int64_t* ptr, int64_t Nx, int64_t R, int64_t T,
+                                 int64_t K, int64_t F, int64_t* chunk_ptr, float* partial, int64_t partial_chunks,
+                                 void* grad_weight, psa_stream_t stream);
+int64_t psa_segment_matmul_bw_chunks(int64_t R);
+int psa_segment_matmul_tile(int* bm, int* bn, int* bk, int* ch);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

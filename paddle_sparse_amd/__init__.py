@@ -78,6 +78,7 @@ if not _running_the_builder():
         ("topk", ("topk", "segment_topk")),
         ("ppr", ("ppr",)),
         ("multi_aggr", ("spmm_multi",)),
+        ("segment_matmul", ("segment_matmul", "typed_matmul")),
     )
 
     __all__ = ["__version__"]

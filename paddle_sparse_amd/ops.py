@@ -423,6 +423,101 @@ def spmm_multi(rowptr: torch.Tensor, col: torch.Tensor, value: Optional[torch.Te
     return out, arg_min, arg_max
 
 
+# ---- segment_matmul: per-type weights over row segments, on MFMA (csrc/segment_matmul.hip) -------------
+
+
+def _segment_matmul_tile() -> Tuple[int, int, int, int]:
+    c = [ctypes.c_int() for _ in range(4)]
+    check(_lib.load().psa_segment_matmul_tile(*(ctypes.addressof(v) for v in c)))
+    return tuple(v.value for v in c)
+
+
+# a tile is BM rows of one segment x BN columns, the reduction runs in steps of BK; the weight gradient cuts a
+# segment into chunks of CH rows
+SEGMENT_MATMUL_BM, SEGMENT_MATMUL_BN, SEGMENT_MATMUL_BK, SEGMENT_MATMUL_CH = _segment_matmul_tile()
+
+
+def segment_matmul_bw_chunks(R: int) -> int:
+    """Chunks the `partial` buffer of the weight gradient must hold for R rows (psa_segment_matmul_bw_chunks)."""
+    return int(_lib.load().psa_segment_matmul_bw_chunks(int(R)))
+
+
+def _segment_matmul_operands(x, ptr, other, index, out_index, who: str):
+    """Checks shared by the two raw ops: (x, ptr, index, out_index, R, T) with `other` = weight or grad."""
+    _gpu(x, "x")
+    _gpu(other, who)
+    ptr = _index(ptr, "ptr")
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"segment_matmul takes float32 or bfloat16 operands (x is {x.dtype})")
+    if other.dtype != x.dtype:
+        raise TypeError(f"x and {who} must have the same dtype (got {x.dtype} and {other.dtype})")
+    if x.dim() != 2:
+        raise ValueError(f"x must be [Nx, K] (got {tuple(x.shape)})")
+    if not x.is_contiguous() or not other.is_contiguous():
+        raise ValueError(f"x and {who} must be contiguous")
+    if ptr.numel() < 1:
+        raise ValueError("ptr must have at least one element")
+    index = None if index is None else _index(index, "index")
+    out_index = None if out_index is None else _index(out_index, "out_index")
+    R = x.shape[0] if index is None else index.numel()
+    if out_index is not None and out_index.numel() != R:
+        raise ValueError(f"out_index must have one entry per row ({R})")
+    return ptr, index, out_index, R, ptr.numel() - 1
+
+
+def segment_matmul(x: torch.Tensor, ptr: torch.Tensor, weight: torch.Tensor, index: Optional[torch.Tensor] = None,
+                   out_index: Optional[torch.Tensor] = None, trans_w: bool = False,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out [R, F] with out_row(r) = x_row(r) @ weight[t] for ptr[t] <= r < ptr[t + 1] (psa_segment_matmul): x_row(r) is
+    x[index[r]] or x[r], out_row(r) is out[out_index[r]] or out[r]; out_index must be injective (not checked).
+    weight is [T, K, F], or with trans_w [T, F, K] read transposed.  float32 or bfloat16 (fp32 sums, one rounding).
+    ptr and the index arrays are trusted; no host read, capturable.  R = ptr[T] is taken from index, or from x."""
+    ptr, index, out_index, R, T = _segment_matmul_operands(x, ptr, weight, index, out_index, "weight")
+    if weight.dim() != 3 or weight.shape[0] != T or weight.shape[2 if trans_w else 1] != x.shape[1]:
+        raise ValueError(f"weight must be [{T}, {'F, K' if trans_w else 'K, F'}] with K = {x.shape[1]} "
+                         f"(got {tuple(weight.shape)})")
+    K, F = x.shape[1], weight.shape[1 if trans_w else 2]
+    if K < 1 or F < 1:
+        raise ValueError("K and F must be at least 1")
+    if out is None:
+        out = torch.empty((R, F), dtype=x.dtype, device=x.device)
+    elif out.dtype != x.dtype or out.shape != (R, F) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"out must be a contiguous {x.dtype} [{R}, {F}] tensor on x's device")
+    tile_ptr = torch.empty(T + 1, dtype=torch.int64, device=x.device)
+    with _on(x.device):
+        check(_lib.load().psa_segment_matmul(_DTYPE_ID[x.dtype], _ptr(x), _ptr(index), _ptr(ptr), _ptr(weight),
+                                             _ptr(out_index), x.shape[0], R, T, K, F, int(bool(trans_w)),
+                                             _ptr(tile_ptr), _ptr(out), _stream()))
+    return out
+
+
+def segment_matmul_bw_weight(x: torch.Tensor, ptr: torch.Tensor, grad: torch.Tensor,
+                             index: Optional[torch.Tensor] = None, out_index: Optional[torch.Tensor] = None,
+                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """grad_weight [T, K, F] = sum over the rows r of segment t of x_row(r)^T (outer) grad_row(r), with x_row(r) as in
+    segment_matmul and grad_row(r) = grad[out_index[r]] or grad[r] (psa_segment_matmul_bw_weight).  Segments above
+    SEGMENT_MATMUL_CH rows run as chunks folded in chunk order: no atomics, the same bits on every run, capturable."""
+    ptr, index, out_index, R, T = _segment_matmul_operands(x, ptr, grad, index, out_index, "grad")
+    if grad.dim() != 2 or grad.shape[0] != R:
+        raise ValueError(f"grad must be [{R}, F] (got {tuple(grad.shape)})")
+    K, F = x.shape[1], grad.shape[1]
+    if K < 1 or F < 1:
+        raise ValueError("K and F must be at least 1")
+    if out is None:
+        out = torch.empty((T, K, F), dtype=x.dtype, device=x.device)
+    elif out.dtype != x.dtype or out.shape != (T, K, F) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"out must be a contiguous {x.dtype} [{T}, {K}, {F}] tensor on x's device")
+    lib = _lib.load()
+    chunks = lib.psa_segment_matmul_bw_chunks(R)
+    chunk_ptr = torch.empty(2 * (T + 1), dtype=torch.int64, device=x.device)
+    partial = torch.empty((chunks, K, F), dtype=torch.float32, device=x.device)
+    with _on(x.device):
+        check(lib.psa_segment_matmul_bw_weight(_DTYPE_ID[x.dtype], _ptr(x), _ptr(index), _ptr(grad), _ptr(out_index),
+                                               _ptr(ptr), x.shape[0], R, T, K, F, _ptr(chunk_ptr), _ptr(partial),
+                                               chunks, _ptr(out), _stream()))
+    return out
+
+
 # ---------------------------------------------------------------------------
 # sort / gather / coalesce building blocks
 # ---------------------------------------------------------------------------
