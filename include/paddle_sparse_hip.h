@@ -1801,6 +1801,44 @@ int psa_segment_matmul_bw_weight(int dtype, const void* x, const int64_t* index,
 int64_t psa_segment_matmul_bw_chunks(int64_t R);
 int psa_segment_matmul_tile(int* bm, int* bn, int* bk, int* ch);
 
+/* ---- typed_spmm: relational aggregation fused with per-type weights, on MFMA, fp32 and bf16.
+ *   out[i] = sum over the stored entries e = (i, j) of type t of scale[e] * x[j] @ weight[t]
+ * evaluated per tile of BM = 64 rows as sum over t of H_t @ weight[t], H_t = (A_t x)[tile rows]: nothing of nnz rows
+ * is formed.  The entries come in PLAN ORDER, by (row / BM, type, row), stable (paddle_sparse_amd/typed_spmm.py
+ * builds the arrays): col int32[nnz] (inside [0, N)), lrow uint8[nnz] (row % BM), scale fp32[nnz] or NULL (ones);
+ * a SEGMENT is the run of one (tile, type): seg_ptr int64[S + 1], seg_type int32[S] (forward), seg_tile int32[S]
+ * (weight gradient); tile_seg_ptr int64[ceil(M / BM) + 1] is the range of segments of every tile.  All of them are
+ * trusted.  x [N, K]; weight [T, K, F], or with trans_w != 0 [T, F, K] read transposed; out [M, F]: row-major,
+ * contiguous, of `dtype` PSA_F32 or PSA_BF16.  H is summed in fp32; for bf16 it is rounded ONCE to bf16 where it
+ * becomes the MFMA operand, the products are summed in fp32 and out is rounded once.  Any K, F >= 1 and any element
+ * alignment (16-byte loads when K and F are multiples of 4, bf16 8, and x and weight are 16-byte aligned).  Every
+ * element of out is written by exactly one thread (zeros for rows without entries); one summation order, no atomics,
+ * no host read: capturable.  A row of the tile without entries of type t meets weight[t] as a row of zeros: a
+ * non-finite weight[t] then gives NaN in every row of a tile that holds type t.
+ *
+ * psa_typed_spmm_bw_weight: grad_weight[t] [K, F] = sum over the segments of type t of H^T @ grad[tile rows], grad
+ * [M, F].  by_type int64[S] lists the segments in (type, tile) order, type_seg_ptr int64[T + 1] its ranges.  A work
+ * item is a chunk of at most CS consecutive segments of one type: work_ptr int64[T + 1] with
+ * max(1, ceil(segments of t / CS)) items per type, `items` = work_ptr[T]; a type with one item writes grad_weight[t]
+ * (zeros without entries), a type with more writes fp32 partials [partial_chunks, K, F] at part_ptr[t] + chunk
+ * (part_ptr int64[T + 1], counting the chunks of those types only), which psa_typed_spmm_bw_fold sums in chunk order.
+ * [K, F] is cut into 64 x 64 tiles, each a workgroup of its own that repeats the gather of its 64 columns of x.
+ * psa_typed_spmm_tile: the constants BM, BK (reduction step), KS (columns of x per slab of H), CS and PASS (entries
+ * of one row and type that one pass of the gather holds). */
+int psa_typed_spmm(int dtype, const void* x, const void* weight, const float* scale, const int32_t* col,
+                   const uint8_t* lrow, const int64_t* seg_ptr, const int32_t* seg_type, const int64_t* tile_seg_ptr,
+                   int64_t M, int64_t N, int64_t nnz, int64_t T, int64_t K, int64_t F, int trans_w, void* out,
+                   psa_stream_t stream);
+int psa_typed_spmm_bw_weight(int dtype, const void* x, const void* grad, const float* scale, const int32_t* col,
+                             const uint8_t* lrow, const int64_t* seg_ptr, const int32_t* seg_tile,
+                             const int64_t* type_seg_ptr, const int64_t* by_type, const int64_t* work_ptr,
+                             const int64_t* part_ptr, int64_t items, int64_t partial_chunks, int64_t M, int64_t N,
+                             int64_t nnz, int64_t T, int64_t K, int64_t F, float* partial, void* grad_weight,
+                             psa_stream_t stream);
+int psa_typed_spmm_bw_fold(int dtype, const int64_t* work_ptr, const int64_t* part_ptr, int64_t T, int64_t K,
+                           int64_t F, const float* partial, void* grad_weight, psa_stream_t stream);
+int psa_typed_spmm_tile(int* bm, int* bk, int* ks, int* cs, int* pass);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

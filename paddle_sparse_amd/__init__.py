@@ -79,6 +79,7 @@ if not _running_the_builder():
         ("ppr", ("ppr",)),
         ("multi_aggr", ("spmm_multi",)),
         ("segment_matmul", ("segment_matmul", "typed_matmul")),
+        ("typed_spmm", ("RelationalPlan", "typed_spmm")),
     )
 
     __all__ = ["__version__"]

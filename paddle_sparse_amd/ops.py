@@ -518,6 +518,94 @@ def segment_matmul_bw_weight(x: torch.Tensor, ptr: torch.Tensor, grad: torch.Ten
     return out
 
 
+# ---- typed_spmm: relational aggregation fused with per-type weights, on MFMA (csrc/typed_spmm.hip) -------------
+
+
+def _typed_spmm_tile() -> Tuple[int, int, int, int, int]:
+    c = [ctypes.c_int() for _ in range(5)]
+    check(_lib.load().psa_typed_spmm_tile(*(ctypes.addressof(v) for v in c)))
+    return tuple(v.value for v in c)
+
+
+# a tile is BM rows; the transform steps BK along the reduction; H holds KS columns of x at a time; the weight
+# gradient cuts the segments of a type into chunks of CS; one pass of the gather holds PASS entries of a wave's rows
+TYPED_SPMM_BM, TYPED_SPMM_BK, TYPED_SPMM_KS, TYPED_SPMM_CS, TYPED_SPMM_PASS = _typed_spmm_tile()
+
+
+def _typed_spmm_operands(plan, x, other, scale, who: str):
+    """Checks shared by the two raw ops; `plan` carries the arrays of typed_spmm.RelationalPlan."""
+    _gpu(x, "x")
+    _gpu(other, who)
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"typed_spmm takes float32 or bfloat16 operands (x is {x.dtype})")
+    if other.dtype != x.dtype:
+        raise TypeError(f"x and {who} must have the same dtype (got {x.dtype} and {other.dtype})")
+    if x.dim() != 2 or x.shape[0] != plan.N or x.shape[1] < 1:
+        raise ValueError(f"x must be [{plan.N}, K] with K >= 1 (got {tuple(x.shape)})")
+    if not x.is_contiguous() or not other.is_contiguous():
+        raise ValueError(f"x and {who} must be contiguous")
+    if x.device != plan.col.device:
+        raise ValueError("x and the plan must live on one device")
+    if scale is not None:
+        _gpu(scale, "scale")
+        if scale.dtype != torch.float32 or scale.shape != (plan.nnz,) or not scale.is_contiguous():
+            raise ValueError(f"scale must be a contiguous float32 [{plan.nnz}] tensor in plan order")
+    return scale
+
+
+def typed_spmm(plan, x: torch.Tensor, weight: torch.Tensor, scale: Optional[torch.Tensor] = None,
+               trans_w: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out [M, F] = sum over the entries e = (i, j) of type t of scale[e] * x[j] @ weight[t] (psa_typed_spmm), over the
+    arrays of a typed_spmm.RelationalPlan; scale is float32 [nnz] IN PLAN ORDER or None.  weight is [T, K, F], or with
+    trans_w [T, F, K] read transposed.  float32 or bfloat16 (fp32 sums; bf16 rounds the aggregated rows once and the
+    result once).  No host read, capturable, the same bits on every run."""
+    scale = _typed_spmm_operands(plan, x, weight, scale, "weight")
+    K = x.shape[1]
+    if weight.dim() != 3 or weight.shape[0] != plan.T or weight.shape[2 if trans_w else 1] != K:
+        raise ValueError(f"weight must be [{plan.T}, {'F, K' if trans_w else 'K, F'}] with K = {K} "
+                         f"(got {tuple(weight.shape)})")
+    F = weight.shape[1 if trans_w else 2]
+    if F < 1:
+        raise ValueError("F must be at least 1")
+    if out is None:
+        out = torch.empty((plan.M, F), dtype=x.dtype, device=x.device)
+    elif out.dtype != x.dtype or out.shape != (plan.M, F) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"out must be a contiguous {x.dtype} [{plan.M}, {F}] tensor on x's device")
+    with _on(x.device):
+        check(_lib.load().psa_typed_spmm(_DTYPE_ID[x.dtype], _ptr(x), _ptr(weight), _ptr(scale), _ptr(plan.col),
+                                         _ptr(plan.lrow), _ptr(plan.seg_ptr), _ptr(plan.seg_type),
+                                         _ptr(plan.tile_seg_ptr), plan.M, plan.N, plan.nnz, plan.T, K, F,
+                                         int(bool(trans_w)), _ptr(out), _stream()))
+    return out
+
+
+def typed_spmm_bw_weight(plan, x: torch.Tensor, grad: torch.Tensor, scale: Optional[torch.Tensor] = None,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """grad_weight [T, K, F] = sum over the segments of type t of H^T @ grad[tile rows] (psa_typed_spmm_bw_weight and,
+    when a type holds more than TYPED_SPMM_CS segments, psa_typed_spmm_bw_fold over fp32 partials in chunk order): no
+    atomics, the same bits on every run, capturable."""
+    scale = _typed_spmm_operands(plan, x, grad, scale, "grad")
+    if grad.dim() != 2 or grad.shape[0] != plan.M or grad.shape[1] < 1:
+        raise ValueError(f"grad must be [{plan.M}, F] with F >= 1 (got {tuple(grad.shape)})")
+    K, F, T = x.shape[1], grad.shape[1], plan.T
+    if out is None:
+        out = torch.empty((T, K, F), dtype=x.dtype, device=x.device)
+    elif out.dtype != x.dtype or out.shape != (T, K, F) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"out must be a contiguous {x.dtype} [{T}, {K}, {F}] tensor on x's device")
+    lib = _lib.load()
+    partial = torch.empty((plan.partial_chunks, K, F), dtype=torch.float32, device=x.device)
+    with _on(x.device):
+        check(lib.psa_typed_spmm_bw_weight(_DTYPE_ID[x.dtype], _ptr(x), _ptr(grad), _ptr(scale), _ptr(plan.col),
+                                           _ptr(plan.lrow), _ptr(plan.seg_ptr), _ptr(plan.seg_tile),
+                                           _ptr(plan.type_seg_ptr), _ptr(plan.by_type), _ptr(plan.work_ptr),
+                                           _ptr(plan.part_ptr), plan.items, plan.partial_chunks, plan.M, plan.N,
+                                           plan.nnz, T, K, F, _ptr(partial), _ptr(out), _stream()))
+        if plan.partial_chunks > 0:
+            check(lib.psa_typed_spmm_bw_fold(_DTYPE_ID[x.dtype], _ptr(plan.work_ptr), _ptr(plan.part_ptr), T, K, F,
+                                             _ptr(partial), _ptr(out), _stream()))
+    return out
+
+
 # ---------------------------------------------------------------------------
 # sort / gather / coalesce building blocks
 # ---------------------------------------------------------------------------
