@@ -1839,6 +1839,42 @@ int psa_typed_spmm_bw_fold(int dtype, const int64_t* work_ptr, const int64_t* pa
                            int64_t F, const float* partial, void* grad_weight, psa_stream_t stream);
 int psa_typed_spmm_tile(int* bm, int* bk, int* ks, int* cs, int* pass);
 
+/* ---- basis_spmm: the RGCN basis decomposition weight[t] = sum over b of comp[t][b] * basis[b], fused with the
+ * aggregation, on MFMA, fp32 and bf16:
+ *   out[i] = sum over the stored entries e = (i, j) of type t of scale[e] * x[j] @ weight[t]
+ *          = sum over b of Z_b[i] @ basis[b],   Z_b[i] = sum over e of row i of scale[e] * comp[etype[e]][b] * x[col[e]]
+ * The entries are read in CSR order: rowptr int64[M + 1], col int32[nnz] (inside [0, N)), etype int32[nnz] (inside
+ * [0, T)), scale fp32[nnz] or NULL (ones), all in that order and trusted.  comp fp32 [T, B]; x [N, K]; basis [B, K, F],
+ * or with trans != 0 [B, F, K] read transposed; out [M, F]: row-major, contiguous, of `dtype` PSA_F32 or PSA_BF16.  Per
+ * tile of BM rows, group of G bases and slab of KB columns a row of x is gathered once and summed into G rows of Z in
+ * fp32; Z is rounded ONCE to bf16 where it becomes the MFMA operand, the products are summed in fp32 and out is
+ * rounded once.  Any B, K, F >= 1 and any element alignment.  Every element of out is written by exactly one thread
+ * (zeros for rows without entries); one summation order, no atomics, no host read: capturable.
+ *
+ * psa_basis_spmm_bw_basis: grad_basis[b] [K, F] = sum over the row tiles of Z_b^T @ grad[tile rows], grad [M, F].  The
+ * row tiles are cut into psa_basis_spmm_bw_chunks(M) chunks of TC tiles; with one chunk grad_basis is written
+ * directly (partial may be NULL), otherwise fp32 partials [chunks, B, K, F] are written (partial_chunks >= chunks)
+ * and psa_basis_spmm_bw_fold sums them in chunk order into grad_basis.
+ *
+ * psa_basis_spmm_bw_comp: s fp32 [nnz, B] with s[e][b] = scale[e] * <x[col[e]], grad[row of e] @ basis[b]^T>; the
+ * product grad[tile rows] @ basis[b]^T is rounded once to bf16 for bf16 operands.  Every element of s is written by
+ * one thread; grad_comp[t] is the sum of the rows of s whose entry has type t, which the caller forms.
+ * psa_basis_spmm_tile: the constants BM, G, KB, PASS (entries one pass of the gather holds) and TC. */
+int psa_basis_spmm(int dtype, const void* x, const void* basis, const float* comp, const float* scale,
+                   const int64_t* rowptr, const int32_t* col, const int32_t* etype, int64_t M, int64_t N, int64_t nnz,
+                   int64_t T, int64_t B, int64_t K, int64_t F, int trans, void* out, psa_stream_t stream);
+int psa_basis_spmm_bw_basis(int dtype, const void* x, const void* grad, const float* comp, const float* scale,
+                            const int64_t* rowptr, const int32_t* col, const int32_t* etype, int64_t M, int64_t N,
+                            int64_t nnz, int64_t T, int64_t B, int64_t K, int64_t F, float* partial,
+                            int64_t partial_chunks, void* grad_basis, psa_stream_t stream);
+int64_t psa_basis_spmm_bw_chunks(int64_t M);
+int psa_basis_spmm_bw_fold(int dtype, const float* partial, int64_t chunks, int64_t B, int64_t K, int64_t F,
+                           void* grad_basis, psa_stream_t stream);
+int psa_basis_spmm_bw_comp(int dtype, const void* x, const void* grad, const void* basis, const float* scale,
+                           const int64_t* rowptr, const int32_t* col, int64_t M, int64_t N, int64_t nnz, int64_t B,
+                           int64_t K, int64_t F, float* s, psa_stream_t stream);
+int psa_basis_spmm_tile(int* bm, int* g, int* kb, int* pass, int* tc);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

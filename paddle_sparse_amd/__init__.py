@@ -80,6 +80,7 @@ if not _running_the_builder():
         ("multi_aggr", ("spmm_multi",)),
         ("segment_matmul", ("segment_matmul", "typed_matmul")),
         ("typed_spmm", ("RelationalPlan", "typed_spmm")),
+        ("basis_spmm", ("BasisPlan", "basis_spmm")),
     )
 
     __all__ = ["__version__"]

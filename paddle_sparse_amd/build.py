@@ -38,12 +38,13 @@ HIPCC_FLAGS = [
 # plain VALU forms; the older sources are left as they were built and measured.  Cost, from the compiler's resource
 # usage: -12 .. +10 VGPRs per kernel (101 kernels, -120 in sum; the four-statistic set stays at 98); time not compared.
 # segment_matmul.hip (MFMA; its VALU work is addresses and one epilogue) is built the same way from the start, and so
-# is typed_spmm.hip, whose gather sums two columns per lane.
+# is typed_spmm.hip, whose gather sums two columns per lane, and basis_spmm.hip, whose gather sums four bases per lane.
 # The feature string is a device target feature; the host pass accepts it silently.
 SOURCE_FLAGS = {
     "spmm_multi.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "segment_matmul.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
     "typed_spmm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "basis_spmm.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

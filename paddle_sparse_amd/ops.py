@@ -606,6 +606,131 @@ def typed_spmm_bw_weight(plan, x: torch.Tensor, grad: torch.Tensor, scale: Optio
     return out
 
 
+# ---- basis_spmm: RGCN's basis decomposition fused with the aggregation, on MFMA (csrc/basis_spmm.hip) ------------
+
+
+def _basis_spmm_tile() -> Tuple[int, int, int, int, int]:
+    c = [ctypes.c_int() for _ in range(5)]
+    check(_lib.load().psa_basis_spmm_tile(*(ctypes.addressof(v) for v in c)))
+    return tuple(v.value for v in c)
+
+
+# a tile is BM rows; G bases share one gather of x; Z holds KB columns of x at a time; one pass of the gather holds
+# PASS entries of a wave's rows; the basis gradient cuts the row tiles into chunks of TC
+BASIS_SPMM_BM, BASIS_SPMM_G, BASIS_SPMM_KB, BASIS_SPMM_PASS, BASIS_SPMM_TC = _basis_spmm_tile()
+
+
+def _basis_spmm_operands(plan, x, other, scale, who: str):
+    """Checks shared by the three raw ops; `plan` carries the arrays of basis_spmm.BasisPlan."""
+    _gpu(x, "x")
+    _gpu(other, who)
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"basis_spmm takes float32 or bfloat16 operands (x is {x.dtype})")
+    if other.dtype != x.dtype:
+        raise TypeError(f"x and {who} must have the same dtype (got {x.dtype} and {other.dtype})")
+    if x.dim() != 2 or x.shape[0] != plan.N or x.shape[1] < 1:
+        raise ValueError(f"x must be [{plan.N}, K] with K >= 1 (got {tuple(x.shape)})")
+    if not x.is_contiguous() or not other.is_contiguous():
+        raise ValueError(f"x and {who} must be contiguous")
+    if x.device != plan.col.device or other.device != x.device:
+        raise ValueError(f"x, {who} and the plan must live on one device")
+    if scale is not None:
+        _gpu(scale, "scale")
+        if scale.dtype != torch.float32 or scale.shape != (plan.nnz,) or not scale.is_contiguous():
+            raise ValueError(f"scale must be a contiguous float32 [{plan.nnz}] tensor in storage order")
+        if scale.device != x.device:
+            raise ValueError("scale and x must live on one device")
+    return scale
+
+
+def _basis_spmm_comp(plan, comp, x):
+    _gpu(comp, "comp")
+    if comp.dtype != torch.float32:
+        raise TypeError(f"comp must be float32 (got {comp.dtype})")
+    if comp.dim() != 2 or comp.shape[0] != plan.T or comp.shape[1] < 1 or not comp.is_contiguous():
+        raise ValueError(f"comp must be a contiguous [{plan.T}, B] tensor with B >= 1 (got {tuple(comp.shape)})")
+    if comp.device != x.device:
+        raise ValueError("comp and x must live on one device")
+    return comp.shape[1]
+
+
+def basis_spmm(plan, x: torch.Tensor, basis: torch.Tensor, comp: torch.Tensor, scale: Optional[torch.Tensor] = None,
+               trans: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out [M, F] = sum over the entries e = (i, j) of type t and the bases b of scale[e] * comp[t, b] * x[j] @ basis[b]
+    (psa_basis_spmm), over the arrays of a basis_spmm.BasisPlan; scale is float32 [nnz] IN STORAGE ORDER or None.
+    basis is [B, K, F], or with trans [B, F, K] read transposed; comp float32 [T, B].  float32 or bfloat16 (fp32 sums;
+    bf16 rounds the aggregated rows once and the result once).  No host read, capturable, the same bits on every run."""
+    scale = _basis_spmm_operands(plan, x, basis, scale, "basis")
+    B, K = _basis_spmm_comp(plan, comp, x), x.shape[1]
+    if basis.dim() != 3 or basis.shape[0] != B or basis.shape[2 if trans else 1] != K:
+        raise ValueError(f"basis must be [{B}, {'F, K' if trans else 'K, F'}] with K = {K} (got {tuple(basis.shape)})")
+    F = basis.shape[1 if trans else 2]
+    if F < 1:
+        raise ValueError("F must be at least 1")
+    if out is None:
+        out = torch.empty((plan.M, F), dtype=x.dtype, device=x.device)
+    elif out.dtype != x.dtype or out.shape != (plan.M, F) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"out must be a contiguous {x.dtype} [{plan.M}, {F}] tensor on x's device")
+    with _on(x.device):
+        check(_lib.load().psa_basis_spmm(_DTYPE_ID[x.dtype], _ptr(x), _ptr(basis), _ptr(comp), _ptr(scale),
+                                         _ptr(plan.rowptr), _ptr(plan.col), _ptr(plan.etype), plan.M, plan.N, plan.nnz,
+                                         plan.T, B, K, F, int(bool(trans)), _ptr(out), _stream()))
+    return out
+
+
+def basis_spmm_bw_basis(plan, x: torch.Tensor, grad: torch.Tensor, comp: torch.Tensor,
+                        scale: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """grad_basis [B, K, F] = sum over the row tiles of Z_b^T @ grad[tile rows] (psa_basis_spmm_bw_basis and, when the
+    matrix holds more than BASIS_SPMM_TC row tiles, psa_basis_spmm_bw_fold over fp32 partials in chunk order): no
+    atomics, the same bits on every run, capturable."""
+    scale = _basis_spmm_operands(plan, x, grad, scale, "grad")
+    B = _basis_spmm_comp(plan, comp, x)
+    if grad.dim() != 2 or grad.shape[0] != plan.M or grad.shape[1] < 1:
+        raise ValueError(f"grad must be [{plan.M}, F] with F >= 1 (got {tuple(grad.shape)})")
+    K, F = x.shape[1], grad.shape[1]
+    if out is None:
+        out = torch.empty((B, K, F), dtype=x.dtype, device=x.device)
+    elif out.dtype != x.dtype or out.shape != (B, K, F) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"out must be a contiguous {x.dtype} [{B}, {K}, {F}] tensor on x's device")
+    lib = _lib.load()
+    chunks = lib.psa_basis_spmm_bw_chunks(plan.M)
+    partial = torch.empty((chunks if chunks > 1 else 0, B, K, F), dtype=torch.float32, device=x.device)
+    with _on(x.device):
+        check(lib.psa_basis_spmm_bw_basis(_DTYPE_ID[x.dtype], _ptr(x), _ptr(grad), _ptr(comp), _ptr(scale),
+                                          _ptr(plan.rowptr), _ptr(plan.col), _ptr(plan.etype), plan.M, plan.N,
+                                          plan.nnz, plan.T, B, K, F, _ptr(partial), partial.shape[0], _ptr(out),
+                                          _stream()))
+        if chunks > 1:
+            check(lib.psa_basis_spmm_bw_fold(_DTYPE_ID[x.dtype], _ptr(partial), chunks, B, K, F, _ptr(out), _stream()))
+    return out
+
+
+def basis_spmm_bw_comp(plan, x: torch.Tensor, grad: torch.Tensor, basis: torch.Tensor,
+                       scale: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """s float32 [nnz, B] in storage order with s[e, b] = scale[e] * <x[col_e], grad[row_e] @ basis[b]^T>
+    (psa_basis_spmm_bw_comp); grad_comp[t] is the sum of the rows of s of type t.  One writer per element, no atomics,
+    the same bits on every run, capturable."""
+    scale = _basis_spmm_operands(plan, x, grad, scale, "grad")
+    _gpu(basis, "basis")
+    K = x.shape[1]
+    if grad.dim() != 2 or grad.shape[0] != plan.M or grad.shape[1] < 1:
+        raise ValueError(f"grad must be [{plan.M}, F] with F >= 1 (got {tuple(grad.shape)})")
+    F = grad.shape[1]
+    if basis.dtype != x.dtype or basis.dim() != 3 or basis.shape[0] < 1 or basis.shape[1:] != (K, F) \
+            or not basis.is_contiguous() or basis.device != x.device:
+        raise ValueError(f"basis must be a contiguous {x.dtype} [B, {K}, {F}] tensor on x's device")
+    B = basis.shape[0]
+    if out is None:
+        out = torch.empty((plan.nnz, B), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or out.shape != (plan.nnz, B) or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"out must be a contiguous float32 [{plan.nnz}, {B}] tensor on x's device")
+    with _on(x.device):
+        check(_lib.load().psa_basis_spmm_bw_comp(_DTYPE_ID[x.dtype], _ptr(x), _ptr(grad), _ptr(basis), _ptr(scale),
+                                                 _ptr(plan.rowptr), _ptr(plan.col), plan.M, plan.N, plan.nnz, B, K, F,
+                                                 _ptr(out), _stream()))
+    return out
+
+
 # ---------------------------------------------------------------------------
 # sort / gather / coalesce building blocks
 # ---------------------------------------------------------------------------
