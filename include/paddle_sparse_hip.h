@@ -1875,6 +1875,63 @@ int psa_basis_spmm_bw_comp(int dtype, const void* x, const void* grad, const voi
                            int64_t K, int64_t F, float* s, psa_stream_t stream);
 int psa_basis_spmm_tile(int* bm, int* g, int* kb, int* pass, int* tc);
 
+/* ---- edge_spmm: SpMM over per-entry feature vectors, fp32 and bf16 (csrc/edge_spmm.hip).
+ * rowptr int64[M + 1], col int64[nnz] in [0, N); x [N, K], edge [nnz, K] in CSR order, out [M, K]: row-major,
+ * contiguous, of `dtype` PSA_F32 or PSA_BF16 (anything else: PSA_ERR_INVALID_ARG).  With op one of
+ *   PSA_EDGE_MUL       m[e, :] = x[col[e], :] * edge[e, :]
+ *   PSA_EDGE_ADD       m[e, :] = x[col[e], :] + edge[e, :]
+ *   PSA_EDGE_ADD_RELU  m[e, :] = v > 0 ? v : (v != v ? v : 0),  v = x[col[e], :] + edge[e, :]   (relu(NaN) = NaN)
+ * out[r, :] is the sum of m over the stored entries of row r; mean != 0 divides that fp32 sum by float(n_r), once.
+ * A row without entries is 0 either way, and out is fully written (also when nnz == 0; M == 0 or K == 0 launches
+ * nothing).  bf16 forms every message and every sum in fp32 and rounds once, to nearest even, where a result is
+ * written: out, grad_x and grad_edge.  No zero skipping: 0 * inf = NaN.
+ * One wave per row reads the row's slab of edge once beside the gather of x; K % 4 == 0 (bf16: % 8) with 16-byte
+ * aligned operands takes 16-byte accesses, anything else element accesses (any K >= 1, any element alignment).
+ * workspace (16-byte aligned; not needed when nnz <= 128) enables the long-row path: rows above 128 entries run as
+ * 128-entry chunks whose fp32 partial rows are added in chunk order.  It is the list and one fp32 partial row of K
+ * per chunk: psa_spmm_heads_workspace_bytes(nnz, 1, K) bytes.  workspace == NULL keeps every row on one wave: the
+ * same semantics, for callers that know that no row is long (such a row must stay below 2^31 entries).
+ *
+ * psa_edge_spmm_bw_x: the gradient wrt x over the CSC view: colptr int64[N + 1], row_csc = row[csr2csc] and
+ * csr2csc, both int64[nnz].  With g[r, :] = grad_out[r, :] * (row_scale ? row_scale[r] : 1) (row_scale f32[M]: the
+ * 1 / float(n_r) of mean; the product is fp32),
+ *   PSA_EDGE_MUL       grad_x[j, :] = sum over the entries e of column j of g[row[e], :] * edge[e, :]
+ *   PSA_EDGE_ADD_RELU  grad_x[j, :] = sum over the entries e of column j of g[row[e], :] where x[j, :] + edge[e, :] > 0
+ * (the mask is formed again from x and edge; x may be NULL for PSA_EDGE_MUL).  PSA_EDGE_ADD is A^T g, which psa_spmm
+ * over the CSC view computes: PSA_ERR_INVALID_ARG here.  grad_x [N, K] is fully written; long columns take the
+ * forward's chunked plan and a workspace of the same size.
+ *
+ * psa_edge_spmm_bw_edge: the gradient wrt edge, in CSR order, one writer per element and no reduction; row int64[nnz]
+ * is the COO row of every entry:
+ *   grad_edge[e, :] = g[row[e], :] * x[col[e], :]  |  g[row[e], :]  |  g[row[e], :] where x[col[e], :] + edge[e, :] > 0
+ * for mul | add | add_relu (col and x may be NULL for add; edge is read by add_relu only).
+ *
+ * Both gradients of PSA_EDGE_ADD_RELU take the mask v > 0 as written: where the message is NaN (the forward gives
+ * NaN) the mask is 0 and the gradient is 0, not grad_out as a relu backward that tests v <= 0 would pass on.
+ *
+ * No float atomics, no host read: bitwise reproducible and capturable.  PSA_ERR_INVALID_ARG: an unknown dtype or
+ * op, mean outside {0, 1}, a negative size, nnz >= 2^38, K >= 2^24, more than 2^33 - 4 rows (columns for bw_x), a
+ * NULL required pointer; PSA_ERR_WORKSPACE: a workspace that is short.
+ * psa_edge_spmm_tile: constants of the launches: the waves of the capped chunk / combine grids (more chunks, or
+ * more listed rows, take a second trip), the lanes of the capped grad_edge grid, and the elements of one K tile
+ * of the 16-byte form for fp32 and for bf16. */
+typedef enum psa_edge_op {
+  PSA_EDGE_MUL = 0,
+  PSA_EDGE_ADD = 1,
+  PSA_EDGE_ADD_RELU = 2
+} psa_edge_op;
+int psa_edge_spmm(int dtype, int op, int mean, const int64_t* rowptr, const int64_t* col, const void* x,
+                  const void* edge, int64_t M, int64_t N, int64_t K, int64_t nnz, void* out, void* workspace,
+                  size_t workspace_bytes, psa_stream_t stream);
+int psa_edge_spmm_bw_x(int dtype, int op, const int64_t* colptr, const int64_t* row_csc, const int64_t* csr2csc,
+                       const void* grad_out, const void* edge, const void* x, const float* row_scale, int64_t M,
+                       int64_t N, int64_t K, int64_t nnz, void* grad_x, void* workspace, size_t workspace_bytes,
+                       psa_stream_t stream);
+int psa_edge_spmm_bw_edge(int dtype, int op, const int64_t* row, const int64_t* col, const void* grad_out,
+                          const void* x, const void* edge, const float* row_scale, int64_t M, int64_t N, int64_t K,
+                          int64_t nnz, void* grad_edge, psa_stream_t stream);
+int psa_edge_spmm_tile(int* chunk_waves, int* entry_lanes, int* tile_f32, int* tile_bf16);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

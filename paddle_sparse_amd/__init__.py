@@ -81,6 +81,7 @@ if not _running_the_builder():
         ("segment_matmul", ("segment_matmul", "typed_matmul")),
         ("typed_spmm", ("RelationalPlan", "typed_spmm")),
         ("basis_spmm", ("BasisPlan", "basis_spmm")),
+        ("edge_spmm", ("edge_spmm",)),
     )
 
     __all__ = ["__version__"]

@@ -334,6 +334,16 @@ SIGNATURES = {
     "psa_basis_spmm_bw_comp": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                        c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p]),
     "psa_basis_spmm_tile": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # dtype, op, mean, rowptr, col, x, edge, M, N, K, nnz, out, workspace, workspace_bytes
+    "psa_edge_spmm": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                              c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # dtype, op, colptr, row_csc, csr2csc, grad_out, edge, x, row_scale, M, N, K, nnz, grad_x, workspace, workspace_bytes
+    "psa_edge_spmm_bw_x": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # dtype, op, row, col, grad_out, x, edge, row_scale, M, N, K, nnz, grad_edge
+    "psa_edge_spmm_bw_edge": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                      c_int64, c_int64, c_int64, c_void_p, c_void_p]),
+    "psa_edge_spmm_tile": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -423,6 +423,108 @@ def spmm_multi(rowptr: torch.Tensor, col: torch.Tensor, value: Optional[torch.Te
     return out, arg_min, arg_max
 
 
+# ---- edge_spmm: SpMM over per-entry feature vectors, fp32 and bf16 (csrc/edge_spmm.hip) ------------------
+
+EDGE_OP_ID = {"mul": 0, "add": 1, "add_relu": 2}  # psa_edge_op
+EDGE_SPMM_DTYPES = (torch.float32, torch.bfloat16)
+
+
+def _edge_spmm_tile() -> Tuple[int, int, int, int]:
+    c = [ctypes.c_int() for _ in range(4)]
+    check(_lib.load().psa_edge_spmm_tile(*(ctypes.addressof(v) for v in c)))
+    return tuple(v.value for v in c)
+
+
+# the kernel file's own constants: waves of the capped chunk / combine grids (more chunks, or more listed rows, take a
+# second trip), lanes of the capped grad_edge grid (a group of them per entry), and the elements of one K tile of the
+# 16-byte form (K % 4 == 0 fp32, K % 8 == 0 bf16; the element form covers 64)
+EDGE_SPMM_CHUNK_WAVES, EDGE_SPMM_ENTRY_LANES, _tile_f32, _tile_bf16 = _edge_spmm_tile()
+EDGE_SPMM_TILE = {torch.float32: _tile_f32, torch.bfloat16: _tile_bf16}
+
+
+def _edge_operands(op: str, dense: torch.Tensor, edge: torch.Tensor, nnz: int, names):
+    """The [*, K] dense operand and the [nnz, K] edge operand of one call, contiguous; (op id, K)."""
+    if op not in EDGE_OP_ID:
+        raise ValueError(f"unknown op {op!r}: choose from mul, add, add_relu")
+    _gpu(dense, names[0])
+    _gpu(edge, names[1])
+    if dense.dtype != edge.dtype or dense.dtype not in EDGE_SPMM_DTYPES:
+        raise TypeError(f"edge_spmm takes {names[0]} and {names[1]} both float32 or both bfloat16 "
+                        f"(got {dense.dtype}, {edge.dtype})")
+    if dense.dim() != 2:
+        raise ValueError(f"{names[0]} must be 2-D [*, K] (got {tuple(dense.shape)})")
+    if edge.dim() != 2 or edge.shape[0] != nnz or edge.shape[1] != dense.shape[1]:
+        raise ValueError(f"{names[1]} must be [{nnz}, {dense.shape[1]}], one row per stored entry (got {tuple(edge.shape)})")
+    return EDGE_OP_ID[op], dense.shape[1]
+
+
+def edge_spmm(rowptr: torch.Tensor, col: torch.Tensor, x: torch.Tensor, edge: torch.Tensor, op: str = "mul",
+              mean: bool = False, no_long_rows: bool = False) -> torch.Tensor:
+    """out [M, K] of x's dtype: the sum over every row's entries of x[col[e]] (*, +, relu of +) edge[e], over n for
+    mean (psa_edge_spmm).  x [N, K] and edge [nnz, K] in CSR order, both float32 or both bfloat16.  no_long_rows: the
+    caller knows that no row has more than LONG_ROW entries; no workspace is then brought."""
+    rowptr, col = _index(rowptr, "rowptr"), _index(col, "col")
+    op_id, K = _edge_operands(op, x, edge, col.numel(), ("x", "edge"))
+    if rowptr.numel() < 1:
+        raise ValueError("rowptr must have at least one element")
+    x, edge = x.contiguous(), edge.contiguous()
+    M, N, nnz = rowptr.numel() - 1, x.shape[0], col.numel()
+    out = torch.empty((M, K), dtype=x.dtype, device=x.device)
+    lib = _lib.load()
+    ws_bytes = 0 if no_long_rows else lib.psa_spmm_heads_workspace_bytes(nnz, 1, K)
+    ws = _workspace(ws_bytes, x.device) if ws_bytes else None
+    with _on(x.device):
+        check(lib.psa_edge_spmm(_DTYPE_ID[x.dtype], op_id, int(bool(mean)), _ptr(rowptr), _ptr(col), _ptr(x), _ptr(edge),
+                                M, N, K, nnz, _ptr(out), _ptr(ws), ws_bytes, _stream()))
+    return out
+
+
+def edge_spmm_bw_x(colptr: torch.Tensor, row_csc: torch.Tensor, csr2csc: torch.Tensor, grad: torch.Tensor,
+                   edge: torch.Tensor, x: torch.Tensor, op: str, row_scale: Optional[torch.Tensor] = None,
+                   no_long_columns: bool = False) -> torch.Tensor:
+    """grad_x [N, K] of edge_spmm for op mul / add_relu, one pass over the CSC view (psa_edge_spmm_bw_x); grad
+    [M, K], row_scale float32 [M] (the 1 / n of mean) or None.  op add is A^T grad: matmul.spmm_transposed_planned."""
+    colptr, row_csc, csr2csc = _index(colptr, "colptr"), _index(row_csc, "row_csc"), _index(csr2csc, "csr2csc")
+    op_id, K = _edge_operands(op, grad, edge, row_csc.numel(), ("grad", "edge"))
+    if op == "add":
+        raise ValueError("edge_spmm_bw_x: op add is the transposed SpMM of grad (matmul.spmm_transposed_planned)")
+    if x.dtype != grad.dtype or x.shape != (colptr.numel() - 1, K):
+        raise ValueError(f"x must be {grad.dtype} [{colptr.numel() - 1}, {K}]")
+    grad, edge, x = grad.contiguous(), edge.contiguous(), x.contiguous()
+    M, N, nnz = grad.shape[0], x.shape[0], row_csc.numel()
+    if row_scale is not None and (row_scale.dtype != torch.float32 or row_scale.shape != (M,)):
+        raise ValueError(f"row_scale must be float32 [{M}]")
+    out = torch.empty((N, K), dtype=grad.dtype, device=grad.device)
+    lib = _lib.load()
+    ws_bytes = 0 if no_long_columns else lib.psa_spmm_heads_workspace_bytes(nnz, 1, K)
+    ws = _workspace(ws_bytes, grad.device) if ws_bytes else None
+    with _on(grad.device):
+        check(lib.psa_edge_spmm_bw_x(_DTYPE_ID[grad.dtype], op_id, _ptr(colptr), _ptr(row_csc), _ptr(csr2csc), _ptr(grad),
+                                     _ptr(edge), _ptr(x), _ptr(row_scale), M, N, K, nnz, _ptr(out), _ptr(ws), ws_bytes,
+                                     _stream()))
+    return out
+
+
+def edge_spmm_bw_edge(row: torch.Tensor, col: torch.Tensor, grad: torch.Tensor, x: torch.Tensor, edge: torch.Tensor,
+                      op: str, row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """grad_edge [nnz, K] of edge_spmm in CSR order, entry-parallel (psa_edge_spmm_bw_edge); row: the COO row ids."""
+    row, col = _index(row, "row"), _index(col, "col")
+    op_id, K = _edge_operands(op, grad, edge, col.numel(), ("grad", "edge"))
+    if x.dtype != grad.dtype or x.dim() != 2 or x.shape[1] != K:
+        raise ValueError(f"x must be {grad.dtype} [N, {K}]")
+    grad, edge, x = grad.contiguous(), edge.contiguous(), x.contiguous()
+    M, N, nnz = grad.shape[0], x.shape[0], col.numel()
+    if row.numel() != nnz:
+        raise ValueError("row and col must have one id per stored entry")
+    if row_scale is not None and (row_scale.dtype != torch.float32 or row_scale.shape != (M,)):
+        raise ValueError(f"row_scale must be float32 [{M}]")
+    out = torch.empty((nnz, K), dtype=grad.dtype, device=grad.device)
+    with _on(grad.device):
+        check(_lib.load().psa_edge_spmm_bw_edge(_DTYPE_ID[grad.dtype], op_id, _ptr(row), _ptr(col), _ptr(grad), _ptr(x),
+                                                _ptr(edge), _ptr(row_scale), M, N, K, nnz, _ptr(out), _stream()))
+    return out
+
+
 # ---- segment_matmul: per-type weights over row segments, on MFMA (csrc/segment_matmul.hip) -------------
 
 
